@@ -7,7 +7,12 @@ hypotheses on this GPU (see DESIGN.md §Measurement for exactly which operators 
 the step). Inputs are resident in HBM before the timed region; the timed region is bracketed
 by a barrier + device synchronisation on both sides and the max over ranks is reported.
 
-Extra legs (outside the timed region, same process):
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the result line. The scans run before the --warmup steps (the
+clock ramp, --prewarm-s) are discarded: the pipeline state is put back to its seeded initial state
+after them, so the timed steps see the same inputs from run to run.
+
+Extra legs, only with --full (outside the timed region, same process; each has a --no-* switch):
   * roofline   — the contract decomposition BinSoftAssign + ScanBinMomentMatch over H
                  hypotheses (responsibilities materialised), timed per kernel with HIP events
                  on the library stream; achieved = algorithmic bytes / time.
@@ -44,6 +49,14 @@ def parse():
     ap.add_argument("--hyps", type=int, default=256, help="total hypotheses per scan (strong scaling)")
     ap.add_argument("--n-az", type=int, default=4096, help="azimuth steps (x16 rings = points)")
     ap.add_argument("--scans", type=int, default=4, help="distinct resident scans cycled through")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs after the timed region (certs-on step and per-stage times, exchange "
+                         "timing at N > 1, rooflines, C5 legs, drop-in leg, CPU baseline); the --no-* options drop "
+                         "single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays the pipeline's "
+                         "getters return: combined belief, per-hypothesis beliefs and poses, IW states, map) as "
+                         "DIR/<name>.npy (float64)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=30.0)
@@ -257,15 +270,21 @@ def main():
     h0, h1 = pipe.h0, pipe.h1
     H = h1 - h0
     hy = make_hypotheses(H_total)
-    pipe.set_beliefs(hy["X_anchor"][h0:h1], hy["z_lin"][h0:h1], hy["L"][h0:h1], hy["h"][h0:h1], hy["stamp"][h0:h1])
-    pipe.set_weights(hy["weights"])
+    map0 = warmup_map_record(ctx, _abi, make_scan(0, n_az=args.n_az), n, B, bins, origin)
+
+    def init_state():  # the seeded initial beliefs, weights, IW states and map
+        pipe.set_beliefs(hy["X_anchor"][h0:h1], hy["z_lin"][h0:h1], hy["L"][h0:h1], hy["h"][h0:h1],
+                         hy["stamp"][h0:h1])
+        pipe.set_weights(hy["weights"])
+        pipe.set_iw(*iw_process_prior(), *iw_meas_prior())
+        pipe.set_map(map0)
+
+    init_state()
     if args.io_given:  # dev: IMU/odom-branch evidence given (isolates the branch's share of the step)
         from gcslam.synth import make_io_evidence
         pipe.set_io_evidence(*make_io_evidence(H))
     else:
         pipe.set_io_mode(True)  # IMU/odom branch evaluated on the device from each scan's odometry + IMU
-    pipe.set_iw(*iw_process_prior(), *iw_meas_prior())
-    pipe.set_map(warmup_map_record(ctx, _abi, make_scan(0, n_az=args.n_az), n, B, bins, origin))
     if dist.world > 1:
         uid = [pipe.comm_unique_id() if dist.rank == 0 else None]
         dist.td.broadcast_object_list(uid, src=0)
@@ -317,6 +336,13 @@ def main():
         ctx.sync()
         if dist.max(time.perf_counter() - t_pw) >= args.prewarm_s:
             break
+    if prewarm_steps:
+        # the prewarm's length is set by the clock, so its scans are discarded: back to the initial
+        # state and scan 0, and the warmup and timed steps compute the same from run to run
+        init_state()
+        count[0] = 0
+        if ingest:
+            pipe.stage_scan(0, scans[0])
     for _ in range(args.warmup):
         step()
     ctx.sync()
@@ -333,8 +359,10 @@ def main():
     elapsed = dist.max(t1 - t0)
     scans_per_s = args.steps / elapsed
     n_gpus = pipe.comm_size() if dist.world > 1 else 1  # the RCCL communicator's size
+    if args.dump_outputs:
+        dump_outputs(pipe, dist, args.dump_outputs)
     exchange = None
-    if dist.world > 1:
+    if args.full and dist.world > 1:
         # the per-scan all-gather's device time (HIP events around ncclAllGather on the pipeline
         # stream), untimed scans after the timed region: median over 20, max over ranks
         xs = []
@@ -369,11 +397,11 @@ def main():
                               "step k stages scan k+1 while scan k computes (three slots in rotation)") if ingest else
                              "scans pre-staged in HBM before the timed region"},
     }
-    if not args.no_extras:  # certs-on step time and per-stage device times (extras_leg)
+    if args.full and not args.no_extras:  # certs-on step time and per-stage device times (extras_leg)
         out_extra = extras_leg(pipe, ctx, dist, step)
     if exchange is not None:
         out["exchange"] = exchange
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         out.update(out_extra)
     ns = max(hs["scans"], 1.0)
     nst = max(hs["stages"], 1.0)
@@ -390,26 +418,48 @@ def main():
         out["ingest_host_ms_per_scan"] = 1e3 * stage_s[0] / max(stage_s[1], 1)
         out["run_scan_host_ms"] = {"mean": 1e3 * float(np.mean(run_s)), "max": 1e3 * float(np.max(run_s))}
 
-    if dist.rank == 0 and not args.no_roofline:
+    if args.full and dist.rank == 0 and not args.no_roofline:
         rng = np.random.default_rng(5)
         xi = np.zeros((H, 6)); xi[:, 0] = 0.1 + rng.normal(0, 0.005, H); xi[:, 5] = 0.03 + rng.normal(0, 0.002, H)
         d0 = {k: _abi.DeviceArray.from_host(ctx, scans[0][k]) for k in ("points", "timestamps", "weights")}
         dbins = _abi.DeviceArray.from_host(ctx, bins)
         out["roofline"] = roofline_leg(ctx, _abi, scans[0], d0, xi, dbins, B, n, H, origin, reps=args.roofline_reps)
-    if dist.rank == 0 and not args.no_roofline:
+    if args.full and dist.rank == 0 and not args.no_roofline:
         out["fused_roofline"] = fused_roofline_leg(ctx, _abi, scans[0], B, n, H, bins, origin)
-    if dist.rank == 0 and not args.no_map:
+    if args.full and dist.rank == 0 and not args.no_map:
         out["c5_map_fuse"] = map_fuse_leg(ctx, _abi, packed=args.map_layout == "packed")
-    if dist.rank == 0 and dist.world == 1 and not args.no_dropin:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_dropin:
         out["dropin"] = dropin_leg(ctx, _abi)
-    if dist.rank == 0 and dist.world == 1 and not args.no_c5:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_c5:
         out["c5"] = c5_leg(ctx, _abi, args)
         out["c5_dense"] = c5_leg(ctx, _abi, args, cap=131072)
         out["c5_shard"] = c5_shard_leg(ctx, _abi, args)
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_leg(args.n_az, H_total, args.cpu_budget_s)
     if dist.rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(pipe, dist, out_dir):
+    """What the last timed step computed, as a caller of the pipeline reads it back: the combined
+    belief, this rank's per-hypothesis beliefs and diagnostics (pose first), the IW states and the
+    map, one float64 DIR/<name>.npy each (about 1.3 MB at 256 hypotheses). At N > 1 every rank
+    writes its own hypotheses' arrays (names ending in _rank<r>) and rank 0 the replicated ones."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    sfx = "_rank%d" % dist.rank if dist.world > 1 else ""
+    for k, v in pipe.get_beliefs().items():
+        arrs["belief_%s%s" % (k, sfx)] = v
+    arrs["hyp_diag" + sfx] = pipe.hyp_diag()
+    if dist.rank == 0:
+        for k, v in pipe.combined().items():
+            arrs["combined_" + k] = v
+        for k, v in pipe.get_iw().items():
+            arrs["iw_" + k] = v
+        for k, v in pipe.get_map().items():
+            arrs["map_" + k] = v
+    for k, v in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def extras_leg(pipe, ctx, dist, step):

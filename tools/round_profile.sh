@@ -11,9 +11,9 @@ rm -rf $out; mkdir -p $out
 rc=0; timeout -k 10 400 python -u -m pytest tests -q -m gpu --timeout 120 --timeout-method thread > $out/gpu_tests.log 2>&1 || rc=$?
 tail -2 $out/gpu_tests.log
 case $rc in 124|134|137|139) echo "gpu tests stopped rc=$rc"; exit $rc;; esac
-timeout -k 10 300 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 400 $out/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python3 bench.py --no-cpu > $out/bench_rocprof.json 2> $out/bench_rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python3 bench.py --full --no-cpu > $out/bench_rocprof.json 2> $out/bench_rocprof.err
 cp "$(find $out/kt -name '*kernel_stats.csv' | head -1)" $out/kernel_stats.csv
 bash tools/pmc_traffic.sh $round
 cp gpurun_out/pmc_traffic_$round.json $out/pmc_traffic.json
