@@ -46,14 +46,25 @@ GC_DEV void wave_conditioning(const double* __restrict__ M, double eps, double* 
 #pragma unroll
   for (int k = 0; k < N - 2; ++k) {
     // column k below the diagonal: A[i][k] on lane i (symmetric: its row's entry k)
-    const double xk = a[k];
-    const double ss = wave_sum(lane >= k + 2 && row ? xk * xk : 0.0);
-    const double x0 = readlane_f64(xk, k + 1);
-    const double sigma = sqrt(fma(x0, x0, ss));
+    double xk = a[k];
+    double ss = wave_sum(lane >= k + 2 && row ? xk * xk : 0.0);
+    double x0 = readlane_f64(xk, k + 1);
     if (ss == 0.0) {  // already tridiagonal in this column (wave-uniform)
       e[k] = x0;
       continue;
     }
+    // a tiny column (|x| below ~1e-100; couplings of 1e-160 give a subnormal ss): its squares lose their
+    // bits and 2 / vᵀv overflows. The reflector does not depend on the column's scale, so it is formed
+    // from the column scaled by a power of two to a largest entry in [0.5, 1), as LAPACK dlarfg rescales
+    // (exact; wave-uniform branch, not taken otherwise)
+    int ex = 0;
+    if (fma(x0, x0, ss) < 1e-200) {
+      frexp(wave_max(lane >= k + 1 && row ? fabs(xk) : 0.0), &ex);
+      xk = ldexp(xk, -ex);
+      x0 = ldexp(x0, -ex);
+      ss = wave_sum(lane >= k + 2 && row ? xk * xk : 0.0);
+    }
+    const double sigma = sqrt(fma(x0, x0, ss));
     const double alpha = x0 >= 0.0 ? -sigma : sigma;
     const double beta = 1.0 / (sigma * (sigma + fabs(x0)));  // 2 / vᵀv
     const double vl = lane > k + 1 && row ? xk : (lane == k + 1 ? x0 - alpha : 0.0);
@@ -73,7 +84,7 @@ GC_DEV void wave_conditioning(const double* __restrict__ M, double eps, double* 
       for (int j = k + 1; j < N; ++j) a[j] = a[j] - (vl * wb[j] + wl * vb[j]);
     }
     wave_lds_sync();  // the next step rewrites vb / wb
-    e[k] = alpha;
+    e[k] = ex ? ldexp(alpha, ex) : alpha;
   }
   // T: d on the diagonal (lane i's a[i]), e[N-2] = A[N-1][N-2]
   double dself = 0.0;

@@ -80,7 +80,11 @@ int32_t gc_ctx_trim(gc_ctx* ctx);
 int32_t gc_ctx_alloc_stats(gc_ctx* ctx, int64_t* h_out6);
 /* Copies on the context's stream. An upload returns once the caller's buffer may be reused: up to
  * 512 KiB it is copied into the context's pinned staging ring and the DMA is left in flight (later work
- * on the stream is ordered after it), larger ones are waited for. A download is waited for. */
+ * on the stream is ordered after it), larger ones are waited for. A download is waited for.
+ * When a staged upload returns, the destination does NOT hold the data yet: only work on the context's
+ * stream is ordered after the copy. A consumer on another stream (or another process reading the buffer)
+ * must gc_ctx_sync first, or wait on an event recorded on the context's stream after the upload
+ * (gc_event_record). */
 int32_t gc_buffer_upload(gc_ctx* ctx, void* d_dst, const void* h_src, uint64_t bytes);
 int32_t gc_buffer_download(gc_ctx* ctx, void* h_dst, const void* d_src, uint64_t bytes);
 int32_t gc_buffer_copy(gc_ctx* ctx, void* d_dst, const void* d_src, uint64_t bytes);

@@ -102,6 +102,46 @@ def raw_sensor_scan(streams, k, t0, first=False, base=None):
     return s
 
 
+def _with(s, **kw):
+    s.update(kw)
+    return s
+
+
+def _plane(s):
+    p = s["points"].copy()
+    p[:, 2] = 0.5
+    return _with(s, points=p)
+
+
+def _corridor(s):
+    p = s["points"].copy()
+    p[:, 1] = np.copysign(1.0, p[:, 1])
+    return _with(s, points=p)
+
+
+# scan mutations of the degenerate-scan cases (tests/test_gpu_degenerate_scans.py): all 48 bins empty, the
+# bins of one half-space empty, every point on the plane z = 0.5, every point on the two walls y = ±1
+MUTATIONS = {
+    "zero_weights": lambda s: _with(s, weights=np.zeros_like(s["weights"])),
+    "half_zero_weights": lambda s: _with(s, weights=np.where(s["points"][:, 0] < 0.0, 0.0, s["weights"])),
+    "plane": _plane,
+    "corridor": _corridor,
+}
+
+
+# name -> build(...) arguments of the degenerate-scan cases. A single ray, and a plane on an empty map, are
+# ill-posed in the reference itself (pose moves 3e-4 / t_wls 1e-6 under a 1-ulp change of the points) and
+# are left out on purpose.
+DEGENERATE = {
+    "empty_map": dict(empty_map=True),
+    "zero_weights": dict(mutate=MUTATIONS["zero_weights"]),
+    "zero_weights_empty_map": dict(empty_map=True, mutate=MUTATIONS["zero_weights"]),
+    "half_zero_weights": dict(empty_map=True, mutate=MUTATIONS["half_zero_weights"]),
+    "plane": dict(mutate=MUTATIONS["plane"]),
+    "corridor": dict(empty_map=True, mutate=MUTATIONS["corridor"]),
+}
+
+
 def build_raw_sensor(H=4, n_az=256, n_scans=20, k0=1, cap=None):
     """build(io="computed") with the reference's real IMU / odometry (raw_sensor_streams) in place of
     the synthetic IMU and odometry; the points stay synthetic (re-timed into each sweep). Scans k0 ..
@@ -129,12 +169,15 @@ def build_raw_sensor(H=4, n_az=256, n_scans=20, k0=1, cap=None):
                 map_record=map_to_record(m0), iw=(nuP, PsiP, nuM, PsiM), streams=streams)
 
 
-def build(H=4, n_az=256, n_scans=3, seed_scan0=0, io="synthetic", cap=None, yaw0=None, hyp_yaws=None, tilt=0.0):
+def build(H=4, n_az=256, n_scans=3, seed_scan0=0, io="synthetic", cap=None, yaw0=None, hyp_yaws=None, tilt=0.0,
+          empty_map=False, mutate=None):
     """io="synthetic": given IMU/odom-branch evidence (ios list); io="computed": the branch is
     evaluated from each scan's odometry + IMU window (ios=None). cap: N_POINTS_CAP (default: the
     scan size, stride 1). yaw0: the world frame turned by yaw0 (warm-up map and odometry);
     hyp_yaws / tilt: the hypotheses' anchor yaws (cycled) and roll/pitch spread
-    (synth.make_hypotheses)."""
+    (synth.make_hypotheses). empty_map: the node's state before its first scan (MapStats.empty, no
+    warm-up: Matrix-Fisher H = 0, every map-side clamp active). mutate: applied to (a copy of) each
+    scan dict the case returns, not to the warm-up scan (MUTATIONS: degenerate weights / geometry)."""
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fl-slam_amd"))
     from gcslam import synth
@@ -146,7 +189,10 @@ def build(H=4, n_az=256, n_scans=3, seed_scan0=0, io="synthetic", cap=None, yaw0
     bins = O.fibonacci_atlas(48)
     hy = synth.make_hypotheses(H, yaws=hyp_yaws, tilt=tilt)
     Lio, hio, cert = synth.make_io_evidence(H)
-    m0 = warmup_map(scans[0], n, cfg.lidar_origin, bins, 0.0 if yaw0 is None else yaw0)
+    m0 = (O.MapStats.empty(bins.shape[0]) if empty_map
+          else warmup_map(scans[0], n, cfg.lidar_origin, bins, 0.0 if yaw0 is None else yaw0))
+    if mutate is not None:
+        scans = scans[:1] + [mutate(dict(s)) for s in scans[1:]]
     nuP, PsiP = O.iw_process_init()
     nuM, PsiM = O.iw_meas_init()
     beliefs = [O.Belief(hy["X_anchor"][i].copy(), hy["z_lin"][i].copy(), hy["L"][i].copy(), hy["h"][i].copy())

@@ -107,6 +107,23 @@ def test_io_branch_on_real_sensor_windows(ctx):
     pipe.close()
 
 
+def test_recorder_raises_in_this_module(ctx):
+    """This module imports _run_and_compare alone (no _report fixture of its own): a parity mismatch must
+    still fail the test. H = 2, 1,024 points, one scan with given IMU/odom evidence; the pipeline is
+    built from the case, the oracle is handed the same case with the evidence L_io / h_io scaled by 1.5
+    (beliefs, IW and map are re-seeded from the device, the given evidence is not)."""
+    from test_gpu_configs import _pipeline
+    case = cases.build(H=2, n_az=64, n_scans=1, io="synthetic")
+    pipe = _pipeline(case, ctx, 2, case["n"], False)
+    wrong = dict(case)
+    wrong["io"] = (1.5 * case["io"][0], 1.5 * case["io"][1], case["io"][2])
+    with pytest.raises(AssertionError, match="scan0 hyp0"):
+        _run_and_compare(ctx, wrong, 2, case["n"], [0, 1], 1, False, pipe=pipe)
+    pipe.close()
+    # the same case unperturbed passes, so the failure above is the perturbation's
+    _run_and_compare(ctx, case, 2, case["n"], [0, 1], 1, False).close()
+
+
 def test_pipeline_on_real_sensor_windows_h4(ctx):
     """H = 4 over 24 consecutive real windows, 16,384-point sweeps, every hypothesis at the C3 bars."""
     case = cases.build_raw_sensor(H=4, n_az=1024, n_scans=N_SCANS, k0=0)
