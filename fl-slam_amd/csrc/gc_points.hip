@@ -7,9 +7,9 @@
 //
 // Layout / mapping: a wave processes 4 points per step; its 64 lanes
 // are 4 point-groups x 16 bin-lanes, bin-lane l owns bins {l, l+16, l+32, ...}. Per-point
-// softmax sums are 16-lane butterflies; per-bin moment accumulators live in VGPRs for the
-// whole chunk and are reduced across groups/waves once, in a fixed order, into one partial
-// record per (hypothesis, chunk). A finalize kernel sums the records in chunk order, so every
+// softmax sums are 16-lane DPP sums (butterflies; in the fused kernel a reduce-scatter over two steps
+// at a time); per-bin moment accumulators live in VGPRs for the whole chunk and are reduced across
+// groups/waves once, in a fixed order, into one partial record per (hypothesis, chunk). A finalize kernel sums the records in chunk order, so every
 // result is bit-reproducible run to run (no float atomics anywhere).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -58,11 +58,19 @@ GC_DEV double group16_sum(double v) {
 // value through the LDS crossbar without touching memory, so a round costs the SIMD one f64 add
 // instead of two DPP moves and an add (the block's VALU slots are its bound; the LDS pipe runs
 // beside them). xor butterfly: lanes a and a ^ k add the same two partials, so all 16 lanes still
-// end with the bit-identical total. GC_ZSUM: 0 = DPP (group16_sum), 1 = four swizzle rounds, 2 = two
-// DPP rounds then two swizzle rounds.
+// end with the bit-identical total.
+// GC_ZSUM: 0 = DPP per step (group16_sum), 1 = four swizzle rounds, 2 = two DPP rounds then two swizzle
+// rounds, 3 = a reduce-scatter over four steps at a time (group16_sum4, after recip1), 4 = over two steps
+// (group16_sum2): the default. Same bits in every mode; H = 256 1.1529 -> 1.1336 ms per step with 4,
+// 1.1351 with 3 (whose kernels also spill more), H = 32 no slower (profiles/r07/ab_bins_zbatch.txt).
+// GC_ZSUM_AHEAD: the mode of the look-ahead instantiation of k_bins_io (short tasks), by default the same.
 #ifndef GC_ZSUM
-#define GC_ZSUM 0
+#define GC_ZSUM 4
 #endif
+#ifndef GC_ZSUM_AHEAD
+#define GC_ZSUM_AHEAD GC_ZSUM
+#endif
+constexpr int kZsumBatched = 3, kZsumBatched2 = 4;
 template <int XOR>
 GC_DEV double swz_f64(double v) {
   constexpr int pat = (XOR << 10) | 0x1F;  // and_mask 0x1F, or_mask 0, xor_mask XOR
@@ -70,21 +78,22 @@ GC_DEV double swz_f64(double v) {
   const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
   return __hiloint2double(hi, lo);
 }
+template <int MODE>
 GC_DEV double group16_sum_bins(double v) {
-#if GC_ZSUM == 0
-  return group16_sum(v);
-#else
-#if GC_ZSUM == 2
-  v += dpp_f64<kDppXor1>(v);
-  v += dpp_f64<kDppXor2>(v);
-#else
-  v += swz_f64<1>(v);
-  v += swz_f64<2>(v);
-#endif
-  v += swz_f64<4>(v);
-  v += swz_f64<8>(v);
-  return v;
-#endif
+  if constexpr (MODE == 1 || MODE == 2) {
+    if constexpr (MODE == 2) {
+      v += dpp_f64<kDppXor1>(v);
+      v += dpp_f64<kDppXor2>(v);
+    } else {
+      v += swz_f64<1>(v);
+      v += swz_f64<2>(v);
+    }
+    v += swz_f64<4>(v);
+    v += swz_f64<8>(v);
+    return v;
+  } else {
+    return group16_sum(v);
+  }
 }
 GC_DEV double group16_max(double v) {
   v = fmax(v, dpp_f64<kDppXor1>(v));
@@ -174,6 +183,59 @@ GC_DEV double recip(double z) {
   r = fma(r, e, r);
   e = fma(-z, r, 1.0);
   return fma(r, e, r);
+}
+// The 16-lane sums of four steps at once, as a reduce-scatter: the butterfly above leaves one number in
+// all 16 lanes of a row and every lane then takes the same reciprocal; here each exchange round halves
+// the values a lane carries, so four steps' sums cost 5 adds and 1 reciprocal instead of 16 and 4.
+//   round 1 (lane bit 0): a lane keeps the step of its own parity of each pair (z0, z1), (z2, z3) and
+//     sends the other to its xor-1 partner: even lanes hold the pair sums of steps 0 and 2, odd lanes
+//     those of steps 1 and 3;
+//   round 2 (lane bit 1): the same on the two results over xor 2. Lane l now holds the quad sum of step
+//     l & 3 (lanes 0, 4, 8, 12: step 0; 1, 5, 9, 13: step 1; 2, 6, 10, 14: step 2; 3, 7, 11, 15: step 3);
+//   rounds 3, 4: row_shl:4 then row_shl:8 (lane l reads lane l + 4, l + 8 of its row; a source past the
+//     row reads 0): lanes of one class only ever meet their own class, so lane q = 0..3 of each row ends
+//     with step q's total (the row mirrors of group16_sum reverse a quad and would mix the steps). The
+//     other lanes hold partial sums nobody reads.
+// Per step the additions are those of the butterfly in its association, ((l0 + l1) + (l2 + l3)) per
+// quad, then (Q0 + Q1) + (Q2 + Q3), with operands swapped at most: the same bits. One recip1 on the
+// lane's own total, then Z and 1/Z of step s go back to the row's 16 lanes by row_newbcast:s, a 64-bit
+// DPP move each (the only DPP control the f64 pipe of gfx90a and later takes on a 64-bit operand).
+constexpr int kDppRowShl4 = 0x104, kDppRowShl8 = 0x108, kDppRowBcast0 = 0x150;
+template <int CTRL>
+GC_DEV double dpp_f64_z(double v) {  // dpp_f64 with 0 for a source lane outside the row
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+template <int LANE>
+GC_DEV double row_bcast_f64(double v) {  // lane LANE of the row to its 16 lanes: one v_mov_b64_dpp
+  return __builtin_amdgcn_update_dpp(0.0, v, kDppRowBcast0 + LANE, 0xF, 0xF, true);
+}
+GC_DEV void group16_sum4(const double (&z)[4], int lane, double (&Z)[4], double (&rZ)[4]) {
+  const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
+  const double a01 = (b0 ? z[1] : z[0]) + dpp_f64<kDppXor1>(b0 ? z[0] : z[1]);
+  const double a23 = (b0 ? z[3] : z[2]) + dpp_f64<kDppXor1>(b0 ? z[2] : z[3]);
+  double q = (b1 ? a23 : a01) + dpp_f64<kDppXor2>(b1 ? a01 : a23);
+  q += dpp_f64_z<kDppRowShl4>(q);
+  q += dpp_f64_z<kDppRowShl8>(q);
+  const double rq = recip1(q);
+  Z[0] = row_bcast_f64<0>(q); rZ[0] = row_bcast_f64<0>(rq);
+  Z[1] = row_bcast_f64<1>(q); rZ[1] = row_bcast_f64<1>(rq);
+  Z[2] = row_bcast_f64<2>(q); rZ[2] = row_bcast_f64<2>(rq);
+  Z[3] = row_bcast_f64<3>(q); rZ[3] = row_bcast_f64<3>(rq);
+}
+// The same over two steps (GC_ZSUM = 4: half the values held across the exchange): round 1 as above, then
+// a lane carries one value. Round 2 is the butterfly's xor 2, which keeps the parity of the lane;
+// rounds 3 and 4 are the row shifts again. Lanes 0 and 1 of each row end with the totals of steps 0, 1.
+GC_DEV void group16_sum2(const double (&z)[2], int lane, double (&Z)[2], double (&rZ)[2]) {
+  const bool b0 = (lane & 1) != 0;
+  double q = (b0 ? z[1] : z[0]) + dpp_f64<kDppXor1>(b0 ? z[0] : z[1]);
+  q += dpp_f64<kDppXor2>(q);
+  q += dpp_f64_z<kDppRowShl4>(q);
+  q += dpp_f64_z<kDppRowShl8>(q);
+  const double rq = recip1(q);
+  Z[0] = row_bcast_f64<0>(q); rZ[0] = row_bcast_f64<0>(rq);
+  Z[1] = row_bcast_f64<1>(q); rZ[1] = row_bcast_f64<1>(rq);
 }
 // A double whose bits the compiler cannot see: two v_mov_b32 at the point of use. In a persistent
 // kernel at 256 VGPRs a plain 64-bit constant is hoisted out of the task loop and spilled, and a
@@ -308,6 +370,26 @@ GC_DEV void exp2s_shift_tab_n(const double (&y)[N], double Mp, double (&out)[N])
     const double p = fma(fma(fma(kExp2C3, r[j], kExp2C2), r[j], kExp2C1), r[j], 1.0);
     const double t = __hiloint2double(__double2hiint(tv[j]) + (ki[j] << 9), __double2loint(tv[j]));
     out[j] = t * p;
+  }
+}
+// exp2s_shift_tab_n left as its two factors, out[j] = t[j] * p[j] (table entry with the exponent spliced
+// in, cubic): for a caller that fuses the product into a sum.
+template <int N, unsigned TAB>
+GC_DEV void exp2s_shift_tab_tp_n(const double (&y)[N], double Mp, double (&t)[N], double (&p)[N]) {
+  double r[N], tv[N];
+  int ki[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const double ks = y[j] + Mp;
+    ki[j] = __double2loint(ks);
+    r[j] = y[j] - (ks - Mp);
+    tv[j] = *reinterpret_cast<const __attribute__((address_space(3))) double*>(
+        reinterpret_cast<lds_cptr>((uintptr_t)TAB) + ((unsigned)(ki[j] & (kExpTab2 - 1)) << 3));
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    p[j] = fma(fma(fma(kExp2C3, r[j], kExp2C2), r[j], kExp2C1), r[j], 1.0);
+    t[j] = __hiloint2double(__double2hiint(tv[j]) + (ki[j] << 9), __double2loint(tv[j]));
   }
 }
 // σ(x) = 1 / (1 + e^{-x}) on the 2048 table (e^{-|x|} clamped at e^{-700} ~ 1e-304)
@@ -1453,16 +1535,21 @@ GC_DEV void bins_task_lp(const FusedArgs& A, int h, int64_t c, double* lds, doub
 // start of the task's last iteration, broadcast through task_slot at the epilogue's first barrier, and
 // the next task's operands are loaded into ahead during the rest of the epilogue (T tasks, H_l
 // hypotheses: ticket t = chunk t / H_l, hypothesis t % H_l).
-// SEL_CHECK: n_sel < 0 asks for the selection here (the non-look-ahead persistent form, which measured
-// better with the launch's selection left in vector registers and this fallback: H = 256 1.1568 against
-// 1.1592 ms with it scalar and given; profiles/r06/ab_bins_epilogue.txt)
-template <int BPL, bool FULL, bool PRE, bool SEL_CHECK = false>
+// n_sel, stride: the launch's selection (selection_of), always given by the caller. The non-look-ahead
+// persistent form measured better with it left in vector registers than moved to scalar ones (H = 256
+// 1.1568 against 1.1592 ms; profiles/r06/ab_bins_epilogue.txt).
+// ZMODE: the softmax normaliser's 16-lane sum (GC_ZSUM); the batched modes run the steps four or two at a
+// time.
+template <int BPL, bool FULL, bool PRE, int ZMODE>
 GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double* rec, unsigned* ctr,
                       unsigned* task_slot, TaskAhead* ahead, unsigned T, int Hl, unsigned* late_next, int bt_task,
-                      int64_t n_sel, int64_t stride) {  // n_sel, stride: the launch's selection (selection_of)
+                      int64_t n_sel, int64_t stride) {
   (void)bt_task;
-  if constexpr (SEL_CHECK)
-    if (n_sel < 0) selection_of(A, &n_sel, &stride);
+  // B = 16 (one bin per lane, every lane full) keeps the per-step sum: its lane partial is a bare
+  // product t p, which the compiler fuses into the butterfly's first add (Z starts as fma(t, p, partner));
+  // the batched first round adds a selected value, which would round the product first: other bits
+  constexpr int ZB = FULL && BPL == 1 ? 1 : ZMODE == kZsumBatched ? 4 : ZMODE == kZsumBatched2 ? 2 : 1;
+  static_assert(kFusedUnr % ZB == 0, "the unrolled block holds whole batches");
   if constexpr (bins_lp(BPL)) {
     bins_task_lp<BPL, FULL, PRE>(A, h, c, lds, rec, ctr, task_slot, ahead, T, Hl, late_next, n_sel, stride);
     return;
@@ -1577,6 +1664,11 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
       }
       lds_wave_sync();
       for (int s8 = 0; s8 < 16; s8 += kFusedUnr) {
+        // Per step (GC_ZSUM 0..2, and B = 16): logits, exps, the 16-lane sum Z and 1/Z, responsibilities,
+        // moments. Kept as it was beside the batched form below, so that these modes compile to the
+        // kernels they were measured as: the block's schedule follows the order of the source, and the same
+        // statements arranged as a batch of one ran 1 % slower at H = 32 (profiles/r07/ab_bins_zbatch.txt)
+        if constexpr (ZB == 1) {
   #pragma unroll
       for (int s = s8; s < s8 + kFusedUnr; ++s) {
         const int pl = s * 4 + g;
@@ -1595,7 +1687,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         double zl = e[0];
   #pragma unroll
         for (int j = 1; j < BPL; ++j) zl += e[j];
-        const double Z = group16_sum_bins(zl);
+        const double Z = group16_sum_bins<ZMODE>(zl);
         const double rZ = recip1(Z);
         double r[BPL];
   #pragma unroll
@@ -1620,6 +1712,72 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
           for (int j = 0; j < BPL; ++j) accx[j][t] = fma(r[j], fk, accx[j][t]);
         }
       }
+        } else {
+        // ZB steps at a time: their logits, exps and in-lane sums, then the 16-lane sums and one reciprocal
+        // (group16_sum4 / group16_sum2), then each step's responsibilities and moments in step order and
+        // with the per-step form's expressions
+  #pragma unroll
+      for (int sb = s8; sb < s8 + kFusedUnr; sb += ZB) {
+        double e[ZB][BPL], x[ZB][BPL], zl[ZB], Z[ZB], rZ[ZB];
+  #pragma unroll
+        for (int u = 0; u < ZB; ++u) {
+          const int pl = (sb + u) * 4 + g;
+          const double d0 = F[(NF + 0) * kFusedFS + pl], d1 = F[(NF + 1) * kFusedFS + pl], d2 = F[(NF + 2) * kFusedFS + pl];
+          double et[BPL], ep[BPL];
+  #pragma unroll
+          for (int j = 0; j < BPL; ++j) {
+            const int b = bl + 16 * j;
+            x[u][j] = fma(d0, Lb[b], fma(d1, Lb[64 + b], d2 * Lb[128 + b]));
+          }
+          exp2s_shift_tab_tp_n<BPL, 8u * 4u * kFusedFS * kFusedNS>(x[u], Mp, et, ep);
+  #pragma unroll
+          for (int j = 0; j < BPL; ++j) e[u][j] = (FULL || bl + 16 * j < B) ? et[j] * ep[j] : 0.0;
+          // the in-lane sum. With every bin lane full each e is a bare product t p, and in the per-step
+          // form the compiler's contraction fuses products of e0 + e1 + .. into the adds: e1 + t0 p0
+          // unrounded, then + t_j p_j unrounded for j >= 2, in every step of every instantiation. Which
+          // products fuse follows the surrounding code (left to the compiler here, it changed from step
+          // to step), so it is written out: Z keeps the per-step form's bits. The masked form adds
+          // selected values, which never fuse.
+          if constexpr (FULL && BPL > 1) {
+            zl[u] = fma(et[0], ep[0], e[u][1]);
+  #pragma unroll
+            for (int j = 2; j < BPL; ++j) zl[u] = fma(et[j], ep[j], zl[u]);
+          } else {
+            zl[u] = e[u][0];
+  #pragma unroll
+            for (int j = 1; j < BPL; ++j) zl[u] += e[u][j];
+          }
+        }
+        if constexpr (ZB == 4) group16_sum4(zl, lane, Z, rZ);
+        else group16_sum2(zl, lane, Z, rZ);
+  #pragma unroll
+        for (int u = 0; u < ZB; ++u) {
+          const int s = sb + u;
+          const int pl = s * 4 + g;
+          const double vf = PAD ? F[(NF + 3) * kFusedFS + pl] : 1.0;
+          const double fb = F[fcol * kFusedFS + pl];
+          double r[BPL];
+  #pragma unroll
+          for (int j = 0; j < BPL; ++j) r[j] = e[u][j] * rZ[u];
+          double rm = r[0];
+  #pragma unroll
+          for (int j = 1; j < BPL; ++j) rm = fmax(rm, r[j]);
+  #pragma unroll
+          for (int j = 0; j < BPL; ++j) entq = fma(r[j] * vf, x[u][j], entq);
+          mxr = fmax(mxr, rm * vf);
+          zst *= PAD ? fma(Z[u] - 1.0, vf, 1.0) : Z[u];
+  #pragma unroll
+          for (int j = 0; j < BPL; ++j)
+            acc4[s % NACC][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(r[j], fb, acc4[s % NACC][j], 0, 0, 0);
+  #pragma unroll
+          for (int t = 0; t < NX; ++t) {
+            const double fk = F[(17 + t) * kFusedFS + pl];
+  #pragma unroll
+            for (int j = 0; j < BPL; ++j) accx[j][t] = fma(r[j], fk, accx[j][t]);
+          }
+        }
+      }
+        }
         int e8;
         zst = frexp(zst, &e8);
         zex += e8;
@@ -1733,12 +1891,12 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_io(FusedArgs A, PipeDev
     const double tt0 = GC_BT_NOW();
 #endif
     if constexpr (AHEAD) {
-      bins_task<BPL, FULL, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T, H,
-                                 nullptr, (int)t, n_sel, stride);
+      bins_task<BPL, FULL, true, GC_ZSUM_AHEAD>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s,
+                                                &ahead, T, H, nullptr, (int)t, n_sel, stride);
     } else {
       unsigned next = 0;
-      bins_task<BPL, FULL, true, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T,
-                                 H, &next, (int)t, n_sel, stride);
+      bins_task<BPL, FULL, true, GC_ZSUM>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead,
+                                          T, H, &next, (int)t, n_sel, stride);
       if (threadIdx.x == 0) task_s = next;
       __syncthreads();
       ahead.t = task_s;
@@ -1769,9 +1927,9 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_fused(FusedArgs A) {
   const int RL = A.B * NF_BASE + REC_EXTRA;
   int64_t n_sel, stride;
   selection_of(A, &n_sel, &stride);
-  bins_task<BPL, FULL, false>(A, blockIdx.y, blockIdx.x, lds,
-                       A.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * RL, nullptr, nullptr, nullptr,
-                       0u, 1, nullptr, -1, n_sel, stride);
+  bins_task<BPL, FULL, false, GC_ZSUM>(A, blockIdx.y, blockIdx.x, lds,
+                                A.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * RL, nullptr, nullptr,
+                                nullptr, 0u, 1, nullptr, -1, n_sel, stride);
 }
 
 // ================================================================ finalize (a6 + certs)
