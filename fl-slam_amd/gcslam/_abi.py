@@ -141,6 +141,8 @@ SIGNATURES = {
     "gc_extract_map_view": [_vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp],
     "gc_associate_primitives_ot": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp],
+    "gc_visual_pose_evidence": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64,
+                                _vp, _vp, _vp, _vp],
 }
 
 GC_PCFG_LEN = 22
@@ -176,6 +178,8 @@ GC_DRIFT_OUT = 3
 GC_FUSION_ROW = 8
 GC_FUSION_OUT = 4
 GC_BARY_CERT = 16
+GC_VPE_PARTS = 26
+GC_VPE_CERT = 4
 
 
 class PipelineDims(C.Structure):

@@ -127,13 +127,16 @@ def extract_atlas_map_view(atlas_map: DevicePrimitiveMap, tile_ids: List[int], m
 
 @dataclass
 class PrimitiveAssociationResult:
-    """primitive_association.py:71-92."""
+    """primitive_association.py:71-92. `device` (set by associate_primitives_ot) holds the same six
+    arrays as the DeviceArrays they were computed into, so a consumer on the device
+    (ops.visual_pose_evidence) reads them in HBM instead of uploading the host copies."""
     responsibilities: np.ndarray
     candidate_pool_indices: np.ndarray
     candidate_tile_ids: np.ndarray
     candidate_slots: np.ndarray
     row_masses: np.ndarray
     cost_matrix: np.ndarray
+    device: Optional[dict] = None
 
 
 def _p95(x: np.ndarray) -> float:
@@ -178,7 +181,7 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
               dev[4].ptr, C.byref(map_view.struct), h_cfg.ctypes.data, out["responsibilities"].ptr,
               out["candidate_pool_indices"].ptr, out["candidate_tile_ids"].ptr, out["candidate_slots"].ptr,
               out["row_masses"].ptr, out["cost_matrix"].ptr, cert_v.ctypes.data, ctx=ctx)
-    res = PrimitiveAssociationResult(**{k: v.download() for k, v in out.items()})
+    res = PrimitiveAssociationResult(**{k: v.download() for k, v in out.items()}, device=out)
     if cert_v[11] == 0 or cert_v[12] == 0:
         return (res, CertBundle.create_exact(chart_id=chart_id, anchor_id=anchor_id),
                 ExpectedEffect(objective_name="primitive_association_ot", predicted=0.0, realized=0.0))

@@ -32,8 +32,12 @@ from .imu_odom_evidence import (ImuDependenceInflationResult, ImuGyroEvidenceRes
                                 imu_vmf_gravity_evidence_time_resolved, odom_dependence_inflation,
                                 odom_quadratic_evidence, odom_velocity_evidence, odom_yawrate_evidence,
                                 planar_z_prior, pose_twist_kinematic_consistency, velocity_z_prior)
+from .visual_pose_evidence import (VisualPoseEvidenceResult, build_visual_pose_evidence_22d, visual_pose_evidence,
+                                   visual_pose_evidence_batched)
 
 __all__ = [
+    "VisualPoseEvidenceResult", "visual_pose_evidence", "visual_pose_evidence_batched",
+    "build_visual_pose_evidence_22d",
     "PointBudgetResult", "point_budget_resample", "DeskewConstantTwistResult",
     "deskew_constant_twist", "BinAtlas", "BinSoftAssignResult", "ScanBinStats",
     "bin_soft_assign", "create_fibonacci_atlas", "point_directions", "scan_bin_moment_match",

@@ -823,6 +823,28 @@ int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, cons
                                    int64_t* d_cand_slot_out, double* d_row_mass_out, double* d_cost_out,
                                    double* h_cert_out);
 
+#define GC_VPE_PARTS 26  /* per hypothesis: L_trans(9) h_trans(3) L_rot(9) h_rot(3) cost_trans cost_rot */
+#define GC_VPE_CERT 4    /* host: [n_valid_meas, n_valid_map, sum_row_masses, mean_row_mass] */
+/* visual_pose_evidence (operators/visual_pose_evidence.py:261-436; translation WLS :74-162, vMF
+   scatter rotation :165-253), batched over H linearisation poses that share one association.
+   N measurement primitives (info form + vMF lobes, as gc_associate_primitives_ot takes them), the
+   association's responsibilities (N, K), pool indices int32 (N, K; clamped into the view, as a JAX
+   gather does) and row masses (N), and the view they index. d_pose6 (H, 6) = [t, rotvec] per
+   hypothesis. Outputs (device, caller-allocated): L_pose (H, 22, 22) = eps_lift I with L_trans at
+   [0:3, 0:3] and L_rot at [3:6, 3:6], h_pose (H, 22) laid out the same way, parts (H, GC_VPE_PARTS).
+   h_cert (host) = GC_VPE_CERT values. With no valid measurement or no valid view entry every
+   hypothesis gets L_pose = eps_lift I, h_pose = 0 and parts = 0 (the reference's empty branch,
+   :297-318). H = 0 fills h_cert only (the pose and output pointers may then be NULL); N = 0 is the
+   empty branch. Sums run in a fixed order: results are bitwise reproducible, and row h of a batch
+   equals the H = 1 call with pose h. GC_ERR_ARG for N < 0, K outside [1, 16], n_lobes outside
+   [1, 8], H < 0 or NULL pointers. */
+int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lobes, const double* d_Lambdas,
+                                const double* d_thetas, const double* d_etas, const uint8_t* d_valid,
+                                const double* d_resp, const int32_t* d_pool_idx, const double* d_row_masses,
+                                const gc_map_view* view, int32_t H, const double* d_pose6, double eps_lift,
+                                double eps_mass, double* d_L_pose, double* d_h_pose, double* d_parts,
+                                double* h_cert);
+
 #ifdef __cplusplus
 }
 #endif
