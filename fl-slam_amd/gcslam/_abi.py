@@ -143,6 +143,8 @@ SIGNATURES = {
                                    _vp, _vp],
     "gc_visual_pose_evidence": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64,
                                 _vp, _vp, _vp, _vp],
+    "gc_extract_lidar_surfels": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 C.POINTER(C.c_int32)],
 }
 
 GC_PCFG_LEN = 22
@@ -180,6 +182,9 @@ GC_FUSION_OUT = 4
 GC_BARY_CERT = 16
 GC_VPE_PARTS = 26
 GC_VPE_CERT = 4
+GC_SURFEL_CFG_LEN = 17
+GC_SURFEL_MAX_CELLS = 16384     # gc_surfel.hip: cell keys are below 2^14
+GC_SURFEL_MAX_OCCUPANTS = 1024  # gc_surfel.hip: bucket slots per cell
 
 
 class PipelineDims(C.Structure):

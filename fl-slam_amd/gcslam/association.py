@@ -149,7 +149,8 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
                             anchor_id: str = "primitive_ot"
                             ) -> Tuple[PrimitiveAssociationResult, CertBundle, ExpectedEffect]:
     """primitive_association.py:239-553. measurement_batch is duck-typed like MeasurementBatch:
-    Lambdas (N,3,3), thetas (N,3), etas (N,L,3), weights (N), valid_mask (N)."""
+    Lambdas (N,3,3), thetas (N,3), etas (N,L,3), weights (N), valid_mask (N). A batch that carries
+    `device` (gcslam.measurement_batch.MeasurementBatch from ops.extract_lidar_surfels) is read in HBM."""
     cfg = config or AssociationConfig()
     if cfg.a_policy not in (MeasurementMassPolicy.UNIFORM, MeasurementMassPolicy.WEIGHT_PROPORTIONAL):
         raise ValueError(f"Unsupported measurement mass policy: {cfg.a_policy}. "
@@ -159,15 +160,27 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
     if cfg.cost_scale_by_median:
         raise ValueError("cost_scale_by_median is not supported by the device path")
     ctx = map_view.ctx
-    valid = np.ascontiguousarray(measurement_batch.valid_mask).reshape(-1).astype(np.uint8)
-    N = valid.shape[0]
-    L = int(np.asarray(measurement_batch.etas).shape[1])
     K = int(cfg.k_assoc)
-    arrs = [np.ascontiguousarray(measurement_batch.Lambdas, np.float64).reshape(N, 9),
-            np.ascontiguousarray(measurement_batch.thetas, np.float64).reshape(N, 3),
-            np.ascontiguousarray(measurement_batch.etas, np.float64).reshape(N, L * 3),
-            np.ascontiguousarray(measurement_batch.weights, np.float64).reshape(N), valid]
-    dev = [_abi.DeviceArray.from_host(ctx, a, a.dtype) for a in arrs]
+    mdev = getattr(measurement_batch, "device", None)
+    if mdev is not None:  # a batch computed on the device (ops.extract_lidar_surfels): read it in place
+        L = int(mdev["etas"].shape[1])
+        N = int(mdev["valid_mask"].shape[0])
+        dev = [_abi.device_input(ctx, mdev["Lambdas"], np.float64, (N, 9)),
+               _abi.device_input(ctx, mdev["thetas"], np.float64, (N, 3)),
+               _abi.device_input(ctx, mdev["etas"], np.float64, (N, L * 3)),
+               _abi.device_input(ctx, mdev["weights"], np.float64, (N,)),
+               _abi.device_input(ctx, mdev["valid_mask"], np.uint8, (N,))]
+        valid = w_host = None  # the p95 diagnostics below fetch the host vectors they need
+    else:
+        valid = np.ascontiguousarray(measurement_batch.valid_mask).reshape(-1).astype(np.uint8)
+        N = valid.shape[0]
+        L = int(np.asarray(measurement_batch.etas).shape[1])
+        arrs = [np.ascontiguousarray(measurement_batch.Lambdas, np.float64).reshape(N, 9),
+                np.ascontiguousarray(measurement_batch.thetas, np.float64).reshape(N, 3),
+                np.ascontiguousarray(measurement_batch.etas, np.float64).reshape(N, L * 3),
+                np.ascontiguousarray(measurement_batch.weights, np.float64).reshape(N), valid]
+        dev = [_abi.DeviceArray.from_host(ctx, a, a.dtype) for a in arrs]
+        w_host = arrs[3]
     out = dict(responsibilities=_abi.DeviceArray(ctx, (N, K)), candidate_pool_indices=_abi.DeviceArray(ctx, (N, K), np.int32),
                candidate_tile_ids=_abi.DeviceArray(ctx, (N, K), np.int64),
                candidate_slots=_abi.DeviceArray(ctx, (N, K), np.int64), row_masses=_abi.DeviceArray(ctx, N),
@@ -187,8 +200,12 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
                 ExpectedEffect(objective_name="primitive_association_ot", predicted=0.0, realized=0.0))
     (defect_a, defect_b, transport, sum_a, sum_b, sum_m, sum_novel, ess, nz_a, nz_b, total_cost) = cert_v[:11]
     # p95 diagnostics (sorted marginals / recency rows), host-side as in the reference's cert build
+    if mdev is not None:
+        valid = dev[4].download()
+        if cfg.a_policy == MeasurementMassPolicy.WEIGHT_PROPORTIONAL:
+            w_host = dev[3].download()
     vf = valid.astype(np.float64)
-    a = (vf * arrs[3] if cfg.a_policy == MeasurementMassPolicy.WEIGHT_PROPORTIONAL else vf) / sum_a
+    a = (vf * w_host if cfg.a_policy == MeasurementMassPolicy.WEIGHT_PROPORTIONAL else vf) / sum_a
     last = map_view.download("last_supported_scan_seq")["last_supported_scan_seq"][res.candidate_pool_indices]
     dt = np.maximum(0, int(cfg.scan_seq) - last).astype(np.float64)
     rd = np.exp(-cfg.recency_decay_lambda * dt)

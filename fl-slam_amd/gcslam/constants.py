@@ -54,6 +54,11 @@ GC_K_MERGE_PAIRS_PER_TILE = 4
 GC_PRIMITIVE_MERGE_MAX_TILE_SIZE = 2048
 GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD = 1e-4
 GC_K_INSERT_TILE = 64
+# MeasurementBatch budgets and the parser's non-finite sentinel
+GC_N_FEAT = 512               # constants.py:350
+GC_N_SURFEL = 1024            # constants.py:353
+GC_VMF_N_LOBES = 3            # constants.py:463
+GC_NONFINITE_SENTINEL = 1e6   # constants.py:257
 
 # PipelineConfig defaults (pipeline.py:118-131; gc_unified.yaml:41-57)
 POWER_BETA_MIN = 0.25

@@ -34,8 +34,11 @@ from .imu_odom_evidence import (ImuDependenceInflationResult, ImuGyroEvidenceRes
                                 planar_z_prior, pose_twist_kinematic_consistency, velocity_z_prior)
 from .visual_pose_evidence import (VisualPoseEvidenceResult, build_visual_pose_evidence_22d, visual_pose_evidence,
                                    visual_pose_evidence_batched)
+from .lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
+from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "SurfelExtractionConfig", "extract_lidar_surfels", "MeasurementBatch", "create_empty_measurement_batch",
     "VisualPoseEvidenceResult", "visual_pose_evidence", "visual_pose_evidence_batched",
     "build_visual_pose_evidence_22d",
     "PointBudgetResult", "point_budget_resample", "DeskewConstantTwistResult",

@@ -845,6 +845,33 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
                                 double eps_mass, double* d_L_pose, double* d_h_pose, double* d_parts,
                                 double* h_cert);
 
+#define GC_SURFEL_CFG_LEN 17
+/* extract_lidar_surfels (operators/lidar_surfel_extraction.py:219-431; MA-hex hash grid
+   common/ma_hex_web.py:221-303; batch rows structures/measurement_batch.py:262-347): the LiDAR
+   slice of a MeasurementBatch from the N deskewed points (N, 3), timestamps (N) and weights (N) of
+   one scan (device). h_cfg (host) = [n_surfel, n_feat, voxel_size_m, hex3d_num_cells_1,
+   hex3d_num_cells_2, hex3d_num_cells_z, hex3d_max_occupants, min_points_per_voxel,
+   sensor_noise_var_per_axis, wishart_nu, wishart_psi_scale, kappa_main_scale, kappa_min, kappa_max,
+   eig_min, eps_lift, n_lobes] (SurfelExtractionConfig :43-62 and GC_VMF_N_LOBES).
+   Outputs (device, caller-allocated, n_total = n_feat + n_surfel rows): Lambdas (n_total, 3, 3),
+   thetas (n_total, 3), etas (n_total, n_lobes, 3), weights (n_total), sources int32 (n_total),
+   source_indices int32 (n_total), valid_mask uint8 (n_total), timestamps (n_total), colors
+   (n_total, 3). Only rows n_feat + j, j < n_valid, are written: the caller fills the arrays with the
+   base batch (or zeros) first, and the camera slice and the tail of the LiDAR slice keep it.
+   d_slot_cells (int32, n_surfel; may be NULL) receives the hash cell each slot came from, -1 past
+   n_valid. h_n_valid (host) = min(valid cells, n_surfel); the call waits for it (the reference's one
+   sync, :206). Points with a coordinate at or beyond 0.1 x 1e6 (the parser's non-finite sentinel) or
+   NaN take no part. Valid cells are taken in ascending cell id; a cell keeps its first
+   max_occupants points in ascending point index; all sums run in a fixed order, so the batch is
+   bitwise reproducible. GC_ERR_ARG for N outside [0, 2^22], a grid size outside [1, 16384] or more
+   than 16384 cells in all, max_occupants outside [1, 1024], n_surfel < 1, voxel_size_m <= 0 or
+   2e5 / voxel_size_m >= 2^31, n_lobes outside [1, 8], or NULL pointers. */
+int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points, const double* d_timestamps,
+                                 const double* d_weights, const double* h_cfg, double* d_Lambdas, double* d_thetas,
+                                 double* d_etas, double* d_weights_out, int32_t* d_sources,
+                                 int32_t* d_source_indices, uint8_t* d_valid_mask, double* d_timestamps_out,
+                                 double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid);
+
 #ifdef __cplusplus
 }
 #endif
