@@ -16,6 +16,7 @@
 #include "gc_internal.h"
 #include "gc_math.h"
 #include "gc_mapslot.h"
+#include "gc_mapupdate.h"
 #include "gc_runs.h"
 
 namespace gc {
@@ -501,37 +502,22 @@ hipError_t launch_fuse_colors(const gc_primitive_map& map, double eps_mass, hipS
   hipLaunchKernelGGL(k_fuse_colors, dim3((unsigned)((map.m_slots + 255) / 256)), dim3(256), 0, st, map, eps_mass);
   return hipGetLastError();
 }
-}  // namespace gc
+// scratch of fuse_launch for K rows: the sorted slot, row order, run length and owner's entry of every
+// position and the apply launch's per-workgroup distinct-slot counts
+size_t fuse_scratch_bytes(int64_t K) {
+  const size_t kv = ((size_t)K * sizeof(uint32_t) + 255) / 256 * 256;
+  const size_t wg = (size_t)(kFuseBlk < kApplyWG ? kFuseBlk : kApplyWG);
+  return 4 * kv + ((size_t)K + wg - 1) / wg * sizeof(uint32_t) + 256;
+}
 
-using namespace gc;
-
-extern "C" {
-
-int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* meas,
-                              const double* h_pose6, double eps_lift, double eps_mass, double timestamp,
-                              int64_t scan_seq, int64_t* n_fused_out) {
-  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
-  if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, map && meas, "NULL map or measurement batch");
-  GC_CHECK_ARG(ctx, map->m_slots > 0 && map->m_slots < (int64_t)kDropped, "m_slots out of range");
-  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobes, "n_lobes must be in [1, 8]");
-  {
-    const char* lay_ = gc::map_layout_error(*map);
-    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
-  }
-  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
-                        map->last_supported_scan_seq && map->last_update_scan_seq,
-               "NULL map field");
-  const bool color = map->cam_mass != nullptr;
-  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
-               "colour fields must be all set or all NULL");
-  GC_CHECK_ARG(ctx, meas->K >= 0 && meas->K < (int64_t)kDropped, "K out of range");
-  if (n_fused_out) *n_fused_out = 0;
+// The launches of gc_primitive_map_fuse on validated arguments with K >= 1 rows (no host wait once the
+// run table has its size): scr holds fuse_scratch_bytes(K). *d_counts / *n_counts: the per-workgroup
+// distinct-slot counts in scr.
+int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* meas, const double* h_pose6,
+                double eps_lift, double eps_mass, double timestamp, int64_t scan_seq, void* scr,
+                uint32_t** d_counts, unsigned* n_counts) {
   const int64_t K = meas->K;
-  if (K == 0) return GC_OK;  // exact no-op (primitive_map.py:1031-1039)
-  GC_CHECK_ARG(ctx, meas->target_slots && meas->Lambdas && meas->thetas && meas->etas && meas->weights &&
-                        meas->responsibilities,
-               "NULL measurement field");
+  const bool color = map->cam_mass != nullptr;
   FuseArgs A{};
   A.map = *map;
   A.meas = *meas;
@@ -562,8 +548,6 @@ int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc
   const bool staged = A.rec32 && GC_FUSE_STAGED;  // k_fuse_apply_blk: one workgroup per sort block
   const unsigned nblk = (unsigned)((K + kFuseBlk - 1) / kFuseBlk);
   const unsigned grid = staged ? nblk : (unsigned)((K + kApplyWG - 1) / kApplyWG);
-  void* scr;
-  if (int rc = gc::scratch(ctx, 4 * kv + (size_t)grid * sizeof(uint32_t), &scr)) return rc;
   char* base = (char*)scr;
   uint32_t* sslot = (uint32_t*)base;
   uint32_t* order = (uint32_t*)(base + kv);
@@ -598,6 +582,47 @@ int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc
                        eps_mass);
     GC_LAUNCH_CHECK(ctx);
   }
+  *d_counts = cnt;
+  *n_counts = grid;
+  return GC_OK;
+}
+}  // namespace gc
+
+using namespace gc;
+
+extern "C" {
+
+int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* meas,
+                              const double* h_pose6, double eps_lift, double eps_mass, double timestamp,
+                              int64_t scan_seq, int64_t* n_fused_out) {
+  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
+  if (int rc_j = gc::join_side(ctx)) return rc_j;
+  GC_CHECK_ARG(ctx, map && meas, "NULL map or measurement batch");
+  GC_CHECK_ARG(ctx, map->m_slots > 0 && map->m_slots < (int64_t)kDropped, "m_slots out of range");
+  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobes, "n_lobes must be in [1, 8]");
+  {
+    const char* lay_ = gc::map_layout_error(*map);
+    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
+  }
+  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
+                        map->last_supported_scan_seq && map->last_update_scan_seq,
+               "NULL map field");
+  const bool color = map->cam_mass != nullptr;
+  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
+               "colour fields must be all set or all NULL");
+  GC_CHECK_ARG(ctx, meas->K >= 0 && meas->K < (int64_t)kDropped, "K out of range");
+  if (n_fused_out) *n_fused_out = 0;
+  const int64_t K = meas->K;
+  if (K == 0) return GC_OK;  // exact no-op (primitive_map.py:1031-1039)
+  GC_CHECK_ARG(ctx, meas->target_slots && meas->Lambdas && meas->thetas && meas->etas && meas->weights &&
+                        meas->responsibilities,
+               "NULL measurement field");
+  void* scr;
+  if (int rc = gc::scratch(ctx, gc::fuse_scratch_bytes(K), &scr)) return rc;
+  uint32_t* cnt = nullptr;
+  unsigned grid = 0;
+  if (int rc = gc::fuse_launch(ctx, map, meas, h_pose6, eps_lift, eps_mass, timestamp, scan_seq, scr, &cnt, &grid))
+    return rc;
   if (n_fused_out) {
     std::vector<uint32_t> c(grid);
     GC_HIP(ctx, hipMemcpyAsync(c.data(), cnt, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

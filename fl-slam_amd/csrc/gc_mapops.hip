@@ -18,6 +18,7 @@
 #include "gc_internal.h"
 #include "gc_math.h"
 #include "gc_mapslot.h"
+#include "gc_mapupdate.h"
 #include "gc_sort.h"
 
 namespace gc {
@@ -136,9 +137,13 @@ __global__ void k_insert_keys(Tile T, int64_t seq, double lam, double* keys, int
 // One workgroup: blocked exclusive prefix of the proposal mask (new ids), then each thread
 // writes its proposals into their eviction slots.
 __global__ void __launch_bounds__(256) k_insert_apply(Tile T, gc_insert_batch B, const int32_t* __restrict__ order,
-                                                      double ts, int64_t seq, int64_t next_id, int32_t* slots_out,
+                                                      double ts, int64_t seq, int64_t next_id0,
+                                                      const int64_t* __restrict__ id_offset, int32_t* slots_out,
                                                       int64_t* ids_out, double* n_ins_out) {
   __shared__ int64_t scan[256];
+  // ids run on from next_id0, plus a count still on the device (gc_primitive_map_update: the
+  // proposals inserted into earlier tiles of the same call)
+  const int64_t next_id = next_id0 + (id_offset ? *id_offset : 0);
   const int t = threadIdx.x;
   const int64_t per = (B.K + 255) / 256;
   const int64_t k0 = t * per, k1 = k0 + per < B.K ? k0 + per : B.K;
@@ -359,6 +364,49 @@ int download(gc_ctx* ctx, void* h, const void* d, size_t bytes) {
 }
 
 }  // namespace
+// scratch of insert_launch on a tile of n_slots: the reduction partials, the retention keys and slot
+// numbers before and after the sort, and the sort's own
+size_t insert_scratch_bytes(int64_t n_slots) {
+  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
+  const size_t vb = ((size_t)n_slots * sizeof(int32_t) + 255) / 256 * 256;
+  return sizeof(double) * (kPartBlocks + 16) + 2 * kb + 2 * vb + gc::sort_temp_bytes(1, n_slots, true);
+}
+
+// The launches of gc_primitive_map_insert_masked on validated arguments (no host wait): scr holds
+// insert_scratch_bytes(n_slots); d_out2 (device) = [valid count of the tile after, n_inserted].
+// d_id_offset (device, or NULL) is added to next_global_id.
+int insert_launch(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots,
+                  const gc_insert_batch* batch, double timestamp, int64_t scan_seq, double recency_decay_lambda,
+                  int64_t next_global_id, const int64_t* d_id_offset, int32_t* d_target_slots_out,
+                  int64_t* d_new_ids_out, void* scr, double* d_out2) {
+  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
+  const size_t vb = ((size_t)n_slots * sizeof(int32_t) + 255) / 256 * 256;
+  const size_t head = sizeof(double) * (kPartBlocks + 16);
+  double* part = (double*)scr;
+  char* base = (char*)scr + head;
+  double* keys_in = (double*)base;
+  double* keys = (double*)(base + kb);
+  int32_t* vals_in = (int32_t*)(base + 2 * kb);
+  int32_t* vals = (int32_t*)(base + 2 * kb + vb);
+  void* tmp = base + 2 * kb + 2 * vb;
+  const Tile T{*map, slot0, n_slots};
+  hipLaunchKernelGGL(k_insert_keys, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, scan_seq,
+                     recency_decay_lambda, keys_in, vals_in);
+  GC_LAUNCH_CHECK(ctx);
+  if (gc::radix_sort_pairs(ctx->stream, keys_in, keys, (const uint32_t*)vals_in, (uint32_t*)vals, 1, n_slots, false,
+                           tmp) != hipSuccess) {
+    gc::set_error(ctx, "radix sort failed");
+    return GC_ERR_RUNTIME;
+  }
+  hipLaunchKernelGGL(k_insert_apply, dim3(1), dim3(256), 0, ctx->stream, T, *batch, (const int32_t*)vals, timestamp,
+                     scan_seq, next_global_id, d_id_offset, d_target_slots_out, d_new_ids_out, d_out2 + 1);
+  GC_LAUNCH_CHECK(ctx);
+  if (int rc = reduce_into<1>(ctx, n_slots, part, d_out2, [&](unsigned nb) {
+        hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, part);
+      }))
+    return rc;
+  return GC_OK;
+}
 }  // namespace gc
 
 using namespace gc;
@@ -467,35 +515,11 @@ int32_t gc_primitive_map_insert_masked(gc_ctx* ctx, const gc_primitive_map* map,
   GC_CHECK_ARG(ctx, n_slots < (int64_t)INT32_MAX, "tile too large");
   GC_CHECK_ARG(ctx, batch->Lambdas && batch->thetas && batch->etas && batch->weights && batch->valid_mask,
                "NULL proposal field");
-  const size_t temp = gc::sort_temp_bytes(1, n_slots, true);
-  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
-  const size_t vb = ((size_t)n_slots * sizeof(int32_t) + 255) / 256 * 256;
-  const size_t head = sizeof(double) * (kPartBlocks + 16);
   void* scr;
-  if (int rc = gc::scratch(ctx, head + 2 * kb + 2 * vb + temp, &scr)) return rc;
-  double* part = (double*)scr;
-  double* out = part + kPartBlocks;  // [count_after, n_inserted]
-  char* base = (char*)scr + head;
-  double* keys_in = (double*)base;
-  double* keys = (double*)(base + kb);
-  int32_t* vals_in = (int32_t*)(base + 2 * kb);
-  int32_t* vals = (int32_t*)(base + 2 * kb + vb);
-  void* tmp = base + 2 * kb + 2 * vb;
-  const Tile T{*map, slot0, n_slots};
-  hipLaunchKernelGGL(k_insert_keys, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, scan_seq,
-                     recency_decay_lambda, keys_in, vals_in);
-  GC_LAUNCH_CHECK(ctx);
-  if (gc::radix_sort_pairs(ctx->stream, keys_in, keys, (const uint32_t*)vals_in, (uint32_t*)vals, 1, n_slots, false,
-                           tmp) != hipSuccess) {
-    gc::set_error(ctx, "radix sort failed");
-    return GC_ERR_RUNTIME;
-  }
-  hipLaunchKernelGGL(k_insert_apply, dim3(1), dim3(256), 0, ctx->stream, T, *batch, (const int32_t*)vals, timestamp,
-                     scan_seq, next_global_id, d_target_slots_out, d_new_ids_out, out + 1);
-  GC_LAUNCH_CHECK(ctx);
-  if (int rc = reduce_into<1>(ctx, n_slots, part, out, [&](unsigned nb) {
-        hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, part);
-      }))
+  if (int rc = gc::scratch(ctx, gc::insert_scratch_bytes(n_slots), &scr)) return rc;
+  double* out = (double*)scr + kPartBlocks;  // [count_after, n_inserted]
+  if (int rc = gc::insert_launch(ctx, map, slot0, n_slots, batch, timestamp, scan_seq, recency_decay_lambda,
+                                 next_global_id, nullptr, d_target_slots_out, d_new_ids_out, scr, out))
     return rc;
   double h[2];
   if (int rc = download(ctx, h, out, sizeof(h))) return rc;

@@ -54,6 +54,9 @@ GC_K_MERGE_PAIRS_PER_TILE = 4
 GC_PRIMITIVE_MERGE_MAX_TILE_SIZE = 2048
 GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD = 1e-4
 GC_K_INSERT_TILE = 64
+GC_H_TILE = 2.0                           # constants.py:408
+GC_M_TILE = GC_PRIMITIVE_MAP_MAX_SIZE     # constants.py:439
+GC_ASSOC_BLOCK_SIZE = 256                 # constants.py:473
 # MeasurementBatch budgets and the parser's non-finite sentinel
 GC_N_FEAT = 512               # constants.py:350
 GC_N_SURFEL = 1024            # constants.py:353

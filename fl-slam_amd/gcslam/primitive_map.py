@@ -3,9 +3,11 @@ primitive_map_fuse (:992-1163) with the world pushforward of transform_gaussian_
 (backend/pipeline.py:1248-1256) fused in (the C5 map update), and the maintenance operators
 primitive_map_insert_masked (:807-982), primitive_map_cull (:1175-1305), primitive_map_forget
 (:1314-1390), primitive_map_recency_inflate (:1400-1490) and primitive_map_merge_reduce
-(:1809-2030). The map lives in HBM as one flat array of n_tiles * m_tile slots (tile t, local
-slot j -> t * m_tile + j); every operator runs in place on its tile. The AtlasMap bookkeeping
-(next_global_id, total_count, per-tile count) stays on the host, as in the reference."""
+(:1809-2030); primitive_map_update_from_association chains them as the post-pose map update of
+backend/pipeline.py:1232-1492 does (step 12b), fuse and novelty insert in one device pass. The map
+lives in HBM as one flat array of n_tiles * m_tile slots (tile t, local slot j -> t * m_tile + j);
+every operator runs in place on its tile. The AtlasMap bookkeeping (next_global_id, total_count,
+per-tile count) stays on the host, as in the reference."""
 
 from __future__ import annotations
 
@@ -16,11 +18,11 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _abi
-from .certificates import CertBundle, ExpectedEffect, InfluenceCert
-from .constants import (GC_CHART_ID, GC_EPS_LIFT, GC_EPS_MASS, GC_EPS_PSD, GC_K_MERGE_PAIRS_PER_TILE,
-                        GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD, GC_PRIMITIVE_FORGETTING_FACTOR,
-                        GC_PRIMITIVE_MERGE_MAX_TILE_SIZE, GC_PRIMITIVE_MERGE_THRESHOLD, GC_RECENCY_DECAY_LAMBDA,
-                        GC_RECENCY_MIN_SCALE)
+from .certificates import CertBundle, ExpectedEffect, InfluenceCert, MapUpdateCert
+from .constants import (GC_ASSOC_BLOCK_SIZE, GC_CHART_ID, GC_EPS_LIFT, GC_EPS_MASS, GC_EPS_PSD, GC_H_TILE,
+                        GC_K_INSERT_TILE, GC_K_MERGE_PAIRS_PER_TILE, GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD,
+                        GC_PRIMITIVE_FORGETTING_FACTOR, GC_PRIMITIVE_MERGE_MAX_TILE_SIZE,
+                        GC_PRIMITIVE_MERGE_THRESHOLD, GC_RECENCY_DECAY_LAMBDA, GC_RECENCY_MIN_SCALE)
 
 GC_VMF_N_LOBES = 3
 
@@ -478,3 +480,227 @@ def primitive_map_merge_reduce(atlas_map: DevicePrimitiveMap, tile_id: int,
     return (PrimitiveMapMergeReduceResult(atlas_map, int(tile_id), n_merged, float(n_merged)), cert,
             ExpectedEffect(objective_name="primitive_map_merge_reduce", predicted=float(max_pairs),
                            realized=float(n_merged)))
+
+
+# ----------------------------------------------------------------------------- the post-pose map update
+GC_MAP_UPDATE_MAX_ROWS = 8192    # include/gcslam.h: the insert plan's LDS holds 13 B per measurement row
+GC_MAP_UPDATE_MAX_INSERT = 1024  # and 13 B per proposal
+GC_MAP_UPDATE_MAX_ACTIVE = 64
+GC_MAP_UPDATE_MAX_K = 64
+_MU_HEAD, _MU_TILE = 4, 8        # GC_MAP_UPDATE_STATS_HEAD / _TILE
+
+_MU_BATCH = (("Lambdas", np.float64, 9), ("thetas", np.float64, 3), ("etas", np.float64, None),
+             ("weights", np.float64, 1), ("valid_mask", np.uint8, 1), ("colors", np.float64, 3),
+             ("sources", np.int32, 1))
+_MU_ASSOC = (("responsibilities", np.float64), ("candidate_tile_ids", np.int64), ("candidate_slots", np.int64),
+             ("row_masses", np.float64))
+
+
+class _MapUpdateIn(C.Structure):
+    _fields_ = [("N", C.c_int64), ("m_tile", C.c_int64), ("K", C.c_int32), ("n_active", C.c_int32),
+                ("k_insert", C.c_int32), ("block_size", C.c_int32)] + \
+               [(k, C.c_void_p) for k, _, _ in _MU_BATCH] + [(k, C.c_void_p) for k, _ in _MU_ASSOC] + \
+               [("active_keys", C.c_void_p), ("active_dense", C.c_void_p), ("h_active_dense", C.c_void_p)]
+
+
+class _MapUpdateOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("insert_indices", "insert_valid", "insert_target_slots", "new_ids",
+                                          "prop_Lambdas", "prop_thetas", "prop_weights", "stats")]
+
+
+@dataclass
+class MapUpdateConfig:
+    """The PipelineConfig fields step 12b reads (pipeline.py:96-160)."""
+    k_insert_tile: int = GC_K_INSERT_TILE
+    h_tile: float = GC_H_TILE
+    block_size: int = GC_ASSOC_BLOCK_SIZE
+    eps_lift: float = GC_EPS_LIFT
+    eps_mass: float = GC_EPS_MASS
+    eps_psd: float = GC_EPS_PSD
+    recency_decay_lambda: float = GC_RECENCY_DECAY_LAMBDA
+    primitive_cull_weight_threshold: float = GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD
+    primitive_forgetting_factor: float = GC_PRIMITIVE_FORGETTING_FACTOR
+    primitive_merge_threshold: float = GC_PRIMITIVE_MERGE_THRESHOLD
+    k_merge_pairs_tile: int = GC_K_MERGE_PAIRS_PER_TILE
+    max_tile_size: int = GC_PRIMITIVE_MERGE_MAX_TILE_SIZE
+
+
+@dataclass
+class PrimitiveMapUpdateResult:
+    """The counters of pipeline.py:930-937 and the insert plan, one row per active tile."""
+    atlas_map: DevicePrimitiveMap
+    n_fused: int
+    n_inserted: int
+    n_culled: int
+    n_merged: int
+    fused_mass_total: float
+    insert_mass_total: float
+    insert_mass_p95: float
+    evicted_mass_total: float
+    insert_indices: np.ndarray       # (n_active, k_insert_tile) int32 measurement rows
+    insert_valid: np.ndarray         # (n_active, k_insert_tile) bool, valid_new after the placeholder rule
+    insert_target_slots: np.ndarray  # (n_active, k_insert_tile) int32 tile-local eviction slots
+    new_ids: np.ndarray              # (n_active, k_insert_tile) int64, -1 where not inserted
+    event_log_entries: Optional[List[dict]] = None
+
+
+def _mu_shape(x):
+    return tuple(x.shape) if isinstance(x, _abi.DeviceArray) else np.shape(x)
+
+
+def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, association_result, measurement_batch,
+                                          active_tile_ids, pose_world, timestamp: float, scan_seq: int,
+                                          config: Optional[MapUpdateConfig] = None,
+                                          map_branch_stats: Optional[dict] = None, maintenance: bool = True,
+                                          event_log: bool = False, chart_id: str = GC_CHART_ID
+                                          ) -> Tuple[PrimitiveMapUpdateResult, CertBundle, ExpectedEffect]:
+    """Step 12b of the reference (backend/pipeline.py:1232-1492) with z_t = pose_world = [t, rotvec]:
+    the per-block, per-tile fuse of the associated rows (:1258-1327), the per-tile novelty insert
+    (:1331-1410), then cull / forget / merge-reduce of every active tile (:1412-1447) and the
+    MapUpdateCert (:1454-1487). active_tile_ids are tile keys of atlas_map in
+    ma_hex_stencil_tile_ids order. The fuse and the inserts run in one device pass
+    (gc_primitive_map_update) with one download at its end; the association's and the batch's
+    `.device` arrays are read in place, host arrays are uploaded. map_branch_stats: the six floats
+    the map branch hands to the certificate (pipeline.py:920-925)."""
+    cfg = config or MapUpdateConfig()
+    ctx = atlas_map.ctx
+    keys = [int(t) for t in active_tile_ids]
+    if len(set(keys)) != len(keys):
+        raise ValueError(f"duplicate active tile ids in {keys}")
+    dense = [atlas_map.dense_tile(t) for t in keys]
+    if any(d < 0 for d in dense):
+        raise ValueError(f"active tile {keys[[d < 0 for d in dense].index(True)]} is not a tile of the map")
+    n_active, k_ins, m_tile = len(keys), int(cfg.k_insert_tile), atlas_map.m_tile
+    adev = getattr(association_result, "device", None)
+    assoc = {k: (adev[k] if adev is not None else getattr(association_result, k)) for k, _ in _MU_ASSOC}
+    if len(_mu_shape(assoc["responsibilities"])) != 2:
+        raise ValueError(f"responsibilities must be (N, K), got {_mu_shape(assoc['responsibilities'])}")
+    N, K = (int(v) for v in _mu_shape(assoc["responsibilities"]))
+    for k in ("candidate_tile_ids", "candidate_slots"):
+        if _mu_shape(assoc[k]) != (N, K):
+            raise ValueError(f"{k} of shape {_mu_shape(assoc[k])}, expected {(N, K)}")
+    if int(np.prod(_mu_shape(assoc["row_masses"]))) != N:
+        raise ValueError(f"row_masses of shape {_mu_shape(assoc['row_masses'])}, expected {(N,)}")
+    mdev = getattr(measurement_batch, "device", None)
+    batch = {}
+    for k, _, _ in _MU_BATCH:
+        v = mdev.get(k) if mdev is not None else getattr(measurement_batch, k, None)
+        if v is None:
+            if k not in ("colors", "sources"):
+                raise ValueError(f"the measurement batch has no {k}")
+            v = np.zeros((N, 3)) if k == "colors" else np.ones(N, np.int32)  # no colour column: all LiDAR
+        batch[k] = v
+    eshape = _mu_shape(batch["etas"])
+    if len(eshape) != 3 or eshape[1] != atlas_map.n_lobes or eshape[2] != 3:
+        raise ValueError(f"etas of shape {eshape}: the map holds {atlas_map.n_lobes} lobes")
+    for k, _, w in _MU_BATCH:
+        n = _mu_shape(batch[k])[0] if len(_mu_shape(batch[k])) else -1
+        if n != N:
+            raise ValueError(f"measurement batch {k} has {n} rows, the association {N}")
+    if not 1 <= k_ins <= min(N, m_tile):
+        raise ValueError(f"k_insert_tile = {k_ins} outside [1, min(N = {N}, m_tile = {m_tile})]")
+    if N > GC_MAP_UPDATE_MAX_ROWS or k_ins > GC_MAP_UPDATE_MAX_INSERT or n_active > GC_MAP_UPDATE_MAX_ACTIVE or \
+            not 1 <= K <= GC_MAP_UPDATE_MAX_K:
+        raise ValueError(f"beyond the insert plan's bounds: N = {N} <= {GC_MAP_UPDATE_MAX_ROWS}, k_insert_tile = "
+                         f"{k_ins} <= {GC_MAP_UPDATE_MAX_INSERT}, {n_active} active tiles <= "
+                         f"{GC_MAP_UPDATE_MAX_ACTIVE}, K = {K} in [1, {GC_MAP_UPDATE_MAX_K}]")
+    pose = np.ascontiguousarray(pose_world, np.float64).reshape(-1)
+    if pose.shape[0] != 6 or not np.all(np.isfinite(pose)):
+        raise ValueError(f"pose_world must be 6 finite values [t, rotvec], got {pose}")
+    if not float(cfg.h_tile) > 0.0:
+        raise ValueError(f"h_tile must be > 0, got {cfg.h_tile}")
+    if int(cfg.block_size) < 1:
+        raise ValueError(f"block_size must be >= 1, got {cfg.block_size}")
+    if "valid_mask" not in atlas_map.ptrs:
+        raise ValueError("the map has no maintenance fields")
+    mb = dict(map_branch_stats or {})
+    L = atlas_map.n_lobes
+    AK = n_active * k_ins
+    n_stats = _MU_HEAD + _MU_TILE * n_active
+    if n_active:
+        h_dense = np.asarray(dense, np.int32)
+        host_in = [batch[k] if isinstance(batch[k], _abi.DeviceArray) else
+                   np.ascontiguousarray(batch[k], dt).reshape((N,) if w == 1 else (N, w or 3 * L))
+                   for k, dt, w in _MU_BATCH] + \
+                  [assoc[k] if isinstance(assoc[k], _abi.DeviceArray) else
+                   np.ascontiguousarray(assoc[k], dt).reshape((N,) if k == "row_masses" else (N, K))
+                   for k, dt in _MU_ASSOC] + [np.asarray(keys, np.int64), h_dense]
+        dts = [dt for _, dt, _ in _MU_BATCH] + [dt for _, dt in _MU_ASSOC] + [np.int64, np.int32]
+        d_in = _abi.upload_many(ctx, host_in, dts)
+        d_out = _abi.alloc_many(ctx, [((AK,), np.int32), ((AK,), np.uint8), ((AK,), np.int32), ((AK,), np.int64),
+                                      ((AK, 9), np.float64), ((AK, 3), np.float64), ((AK,), np.float64),
+                                      ((n_stats,), np.float64)])
+        s_in = _MapUpdateIn(N, m_tile, K, n_active, k_ins, int(cfg.block_size), *[d.ptr for d in d_in],
+                            h_dense.ctypes.data)
+        s_out = _MapUpdateOut(*[d.ptr for d in d_out])
+        h_cfg = np.array([cfg.eps_lift, cfg.eps_mass, cfg.h_tile, cfg.recency_decay_lambda], np.float64)
+        _abi.call("gc_primitive_map_update", ctx.handle, C.byref(atlas_map.struct()), C.byref(s_in), pose.ctypes.data,
+                  h_cfg.ctypes.data, float(timestamp), int(scan_seq), int(atlas_map.next_global_id), C.byref(s_out),
+                  ctx=ctx)
+        idx, val, slots, ids, pL, pth, pw, stats = _abi.download_many(d_out)  # the one download
+    else:
+        idx, val, slots, ids = (np.zeros(0, t) for t in (np.int32, np.uint8, np.int32, np.int64))
+        pL, pth, pw, stats = np.zeros((0, 9)), np.zeros((0, 3)), np.zeros(0), np.zeros(n_stats)
+    tiles = stats[_MU_HEAD:].reshape(n_active, _MU_TILE)
+    n_fused = n_active * int(stats[1])
+    n_inserted, mass_total, mass_p95 = 0, 0.0, 0.0
+    for a, d in enumerate(dense):
+        n_ins = int(tiles[a, 1])
+        atlas_map.tile_count[d] = int(tiles[a, 0])
+        atlas_map.total_count += n_ins
+        atlas_map.next_global_id += n_ins
+        n_inserted += n_ins
+        mass_total += float(tiles[a, 2])            # pipeline.py:1366
+        mass_p95 = max(mass_p95, float(tiles[a, 3]))  # :1367-1371
+        if "cam_mass" in atlas_map.ptrs:
+            atlas_map._tile_cc[d] = True            # the fuse left every slot of the tile at its estimate
+            if n_ins > 0:
+                atlas_map.colors_stale(d)           # inserted colours are clip(c), as primitive_map_insert_masked
+    entries: Optional[List[dict]] = None
+    if event_log:  # pipeline.py:1393-1410: every proposal of a tile that inserted any
+        entries = []
+        col = _abi.host(batch["colors"]).reshape(N, 3)
+        for a in range(n_active):
+            if int(tiles[a, 1]) <= 0:
+                continue
+            sl = slice(a * k_ins, (a + 1) * k_ins)
+            mu = np.linalg.solve(pL[sl].reshape(-1, 3, 3) + cfg.eps_lift * np.eye(3)[None], pth[sl][..., None])[..., 0]
+            for q in range(k_ins):
+                entries.append({"tile_id": keys[a], "mu_world": mu[q].tolist(), "weight": float(pw[sl][q]),
+                                "color": col[idx[sl][q]].tolist(), "timestamp": float(timestamp)})
+    n_culled, n_merged, evicted = 0, 0, 0.0
+    if maintenance:  # pipeline.py:1412-1447, per active tile in order
+        for d in dense:
+            rc, _, _ = primitive_map_cull(atlas_map, d, cfg.primitive_cull_weight_threshold, chart_id=chart_id)
+            n_culled += int(rc.n_culled)
+            evicted += float(rc.mass_dropped)
+            primitive_map_forget(atlas_map, d, cfg.primitive_forgetting_factor, chart_id=chart_id)
+            rm, _, _ = primitive_map_merge_reduce(atlas_map, d, cfg.primitive_merge_threshold,
+                                                  int(cfg.k_merge_pairs_tile), int(cfg.max_tile_size), cfg.eps_psd,
+                                                  cfg.eps_lift, chart_id=chart_id,
+                                                  anchor_id="primitive_map_merge_reduce")
+            n_merged += int(rm.n_merged)
+    result = PrimitiveMapUpdateResult(
+        atlas_map=atlas_map, n_fused=n_fused, n_inserted=n_inserted, n_culled=n_culled, n_merged=n_merged,
+        fused_mass_total=float(stats[0]), insert_mass_total=mass_total, insert_mass_p95=mass_p95,
+        evicted_mass_total=evicted, insert_indices=idx.reshape(n_active, k_ins).copy(),
+        insert_valid=val.reshape(n_active, k_ins).astype(bool),
+        insert_target_slots=slots.reshape(n_active, k_ins).copy(), new_ids=ids.reshape(n_active, k_ins).copy(),
+        event_log_entries=entries)
+    active = set(keys)
+    inactive = [int(t) for t in atlas_map.tile_keys if int(t) not in active]
+    hits = len([t for t in keys if t in atlas_map.tile_keys])
+    cert = CertBundle.create_exact(chart_id=chart_id, anchor_id="map_update", map_update=MapUpdateCert(
+        n_active_tiles=n_active, tile_ids_active=list(keys), n_inactive_tiles=len(inactive),
+        tile_ids_inactive=inactive, tile_cache_hits=hits, tile_cache_misses=len(active) - hits,
+        candidate_tiles_per_meas_mean=float(mb.get("candidate_tiles_per_meas_mean", 0.0)),
+        candidate_primitives_per_meas_mean=float(mb.get("candidate_primitives_per_meas_mean", 0.0)),
+        candidate_primitives_per_meas_p95=float(mb.get("candidate_primitives_per_meas_p95", 0.0)),
+        insert_count_total=n_inserted, insert_mass_total=mass_total, insert_mass_p95=mass_p95,
+        evicted_count=n_culled, evicted_mass_total=evicted, fused_count=n_fused,
+        fused_mass_total=float(stats[0]), merged_count=n_merged,
+        staleness_inflation_strength=float(mb.get("staleness_inflation_strength", 0.0)),
+        staleness_cov_inflation_trace=float(mb.get("staleness_cov_inflation_trace", 0.0)),
+        stale_precision_downscale_total=float(mb.get("stale_precision_downscale_total", 0.0))))
+    return result, cert, ExpectedEffect(objective_name="primitive_map_update", predicted=float(n_active * k_ins),
+                                        realized=float(n_inserted))

@@ -776,6 +776,85 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
                                       int64_t* h_out2);
 
 /* ------------------------------------------------------------------------------------------
+ * The post-pose map update (backend/pipeline.py:1232-1392, step 12b): the fuse of the N x K
+ * associated rows into the active tiles, then the per-tile novelty insert, with no host wait
+ * between the first launch and the last insert.
+ *
+ * Bounds (the insert plan keeps one workgroup's scores, in-tile flags and proposals in LDS:
+ * 13 B per measurement row and 13 B per proposal of the CU's 160 KiB):
+ *   1 <= N <= GC_MAP_UPDATE_MAX_ROWS, 1 <= k_insert <= min(N, m_tile, GC_MAP_UPDATE_MAX_INSERT),
+ *   1 <= n_active <= GC_MAP_UPDATE_MAX_ACTIVE, 1 <= K <= 64.
+ * ------------------------------------------------------------------------------------------ */
+#define GC_MAP_UPDATE_MAX_ROWS 8192
+#define GC_MAP_UPDATE_MAX_INSERT 1024
+#define GC_MAP_UPDATE_MAX_ACTIVE 64
+/* per-call statistics (device doubles): [0] fused_mass_total, [1] sum over blocks of the distinct
+   in-range slot numbers of the block (n_fused = n_active x this), [2..3] unused, then per active
+   tile a at GC_MAP_UPDATE_STATS_HEAD + GC_MAP_UPDATE_STATS_TILE * a: [0] valid count of the tile
+   after its insert, [1] n_inserted, [2] sum of weights_ins, [3] sorted weights_ins at the p95 index,
+   [4] measurement rows in the tile, [5] 1 when the placeholder rule applied */
+#define GC_MAP_UPDATE_STATS_HEAD 4
+#define GC_MAP_UPDATE_STATS_TILE 8
+
+/* The measurement batch (measurement_batch.py:68-134) and the association result
+   (primitive_association.py:71-92), all in device memory, and the active tiles: their keys
+   (device) and the dense tile of each in the map (device and host copies of the same list). */
+typedef struct gc_map_update_in {
+  int64_t N;                          /* measurement rows */
+  int64_t m_tile;                     /* slots per tile: tile d = slots [d * m_tile, (d + 1) * m_tile) */
+  int32_t K;                          /* candidates per row */
+  int32_t n_active;
+  int32_t k_insert;                   /* K_INSERT_TILE */
+  int32_t block_size;                 /* GC_ASSOC_BLOCK_SIZE */
+  const double* Lambdas;              /* (N, 3, 3) body frame */
+  const double* thetas;               /* (N, 3) */
+  const double* etas;                 /* (N, n_lobes, 3) */
+  const double* weights;              /* (N) */
+  const uint8_t* valid_mask;          /* (N) */
+  const double* colors;               /* (N, 3) */
+  const int32_t* sources;             /* (N) 0 = camera, 1 = lidar */
+  const double* responsibilities;     /* (N, K) */
+  const int64_t* candidate_tile_ids;  /* (N, K) tile keys */
+  const int64_t* candidate_slots;     /* (N, K) tile-local slots */
+  const double* row_masses;           /* (N) */
+  const int64_t* active_keys;         /* (n_active) device */
+  const int32_t* active_dense;        /* (n_active) device */
+  const int32_t* h_active_dense;      /* (n_active) host: distinct, each in [0, m_slots / m_tile) */
+} gc_map_update_in;
+
+/* Device outputs, each (n_active, k_insert) unless noted; the caller allocates them. */
+typedef struct gc_map_update_out {
+  int32_t* insert_indices;       /* the chosen measurement rows: the first k_insert of a stable descending
+                                    sort of the tile's score (pipeline.py:1351-1352) */
+  uint8_t* insert_valid;         /* valid_new, after the placeholder rule (:1353-1355) */
+  int32_t* insert_target_slots;  /* the tile-local eviction slot of each proposal */
+  int64_t* new_ids;              /* -1 where not inserted */
+  double* prop_Lambdas;          /* (n_active, k_insert, 3, 3) proposals in the world frame (:1373-1375) */
+  double* prop_thetas;           /* (n_active, k_insert, 3) */
+  double* prop_weights;          /* weights_ins (:1360-1362) */
+  double* stats;                 /* (GC_MAP_UPDATE_STATS_HEAD + GC_MAP_UPDATE_STATS_TILE * n_active) */
+} gc_map_update_out;
+
+/* Fuse (pipeline.py:1258-1327): rows in blocks of block_size as block_associations_for_fuse
+   (primitive_association.py:561-588); every (row, k) whose candidate tile is active, whose
+   measurement is valid and whose slot is in range is pushed to the world frame at h_pose6 = z_t
+   (:1248-1256) and fused with its responsibility into slot dense tile x m_tile + slot, each slot's
+   rows summed in row order. Then every in-range slot number that any candidate of any row names is
+   stamped in every active tile (each per-tile fuse receives all of its block's target slots,
+   :1302-1324 with primitive_map.py:1112) and every slot of the active tiles gets the fuse's colour
+   estimate. Insert plan (:1331-1392): novelty = max(valid / max(sum valid, eps_mass) - row_masses,
+   0), score = novelty w - (1 - valid) 1e6, the measurement's tile from its world mean
+   (tiling.py:126-145); per active tile the first k_insert rows of a stable descending sort of the
+   in-tile scores (others -1e30), valid_new = in_tile & score > -1e20 or all ones when none is, the
+   proposals pushed to the world frame and inserted as gc_primitive_map_insert_masked does, tiles in
+   the given order on the map the fuse left, global ids running on from next_global_id.
+   h_cfg (host) = [eps_lift, eps_mass, h_tile, recency_decay_lambda]. Nothing is downloaded and the
+   stream is not waited for: the caller reads the outputs after its own download. */
+int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const gc_map_update_in* in,
+                                const double* h_pose6, const double* h_cfg, double timestamp, int64_t scan_seq,
+                                int64_t next_global_id, const gc_map_update_out* out);
+
+/* ------------------------------------------------------------------------------------------
  * Map view + OT association (the current PrimitiveMap pose-evidence path).
  * ------------------------------------------------------------------------------------------ */
 /* AtlasMapView (primitive_map.py:236-300) in device memory: V = n_tiles * m_tile_view entries,
