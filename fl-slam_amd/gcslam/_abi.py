@@ -146,6 +146,10 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp],
     "gc_extract_lidar_surfels": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  C.POINTER(C.c_int32)],
+    "gc_lidar_depth_evidence": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gc_camera_measurement_batch": [_vp, _i64, _vp, _vp, _vp, _i64] + [_vp] * 11 + [_vp, _vp, _f64, _f64, _i32, _i32,
+                                                                                    _i32, _f64] + [_vp] * 14,
+    "gc_measurement_batch_from_camera_splats": [_vp, _i64] + [_vp] * 7 + [_i32, _i32, _i32, _f64] + [_vp] * 9,
 }
 
 GC_PCFG_LEN = 22
@@ -186,6 +190,12 @@ GC_VPE_CERT = 4
 GC_SURFEL_CFG_LEN = 17
 GC_SURFEL_MAX_CELLS = 16384     # gc_surfel.hip: cell keys are below 2^14
 GC_SURFEL_MAX_OCCUPANTS = 1024  # gc_surfel.hip: bucket slots per cell
+GC_CAM_CFG_LEN = 23
+GC_CAM_EV = 9
+GC_CAM_MAX_NEAR = 1024          # gc_camsplat.hip: in-radius LiDAR points one query can hold
+GC_CAM_MAX_POINTS = 1 << 22
+GC_CAM_MAX_QUERIES = 4096
+GC_CAM_MAX_FIT_POINTS = 256     # gc_camsplat.hip: one fitted point per thread
 
 
 class PipelineDims(C.Structure):

@@ -35,9 +35,15 @@ from .imu_odom_evidence import (ImuDependenceInflationResult, ImuGyroEvidenceRes
 from .visual_pose_evidence import (VisualPoseEvidenceResult, build_visual_pose_evidence_22d, visual_pose_evidence,
                                    visual_pose_evidence_batched)
 from .lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
+from .camera_splats import (CameraFeatures, CameraSplatDiagnostics, LidarCameraDepthFusionConfig, PinholeIntrinsics,
+                            camera_measurement_batch, feature_list_to_camera_batch, lidar_depth_evidence,
+                            measurement_batch_from_camera_splats)
 from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "CameraFeatures", "CameraSplatDiagnostics", "LidarCameraDepthFusionConfig", "PinholeIntrinsics",
+    "camera_measurement_batch", "feature_list_to_camera_batch", "lidar_depth_evidence",
+    "measurement_batch_from_camera_splats",
     "SurfelExtractionConfig", "extract_lidar_surfels", "MeasurementBatch", "create_empty_measurement_batch",
     "VisualPoseEvidenceResult", "visual_pose_evidence", "visual_pose_evidence_batched",
     "build_visual_pose_evidence_22d",

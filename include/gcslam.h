@@ -951,6 +951,80 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
                                  int32_t* d_source_indices, uint8_t* d_valid_mask, double* d_timestamps_out,
                                  double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid);
 
+#define GC_CAM_CFG_LEN 23    /* LidarCameraDepthFusionConfig in field order
+                                (frontend/sensors/lidar_camera_depth_fusion.py:29-63):
+                                [depth_fusion_weight_camera, depth_fusion_weight_lidar, gamma_lidar,
+                                lidar_projection_radius_pix, lidar_plane_fit_min_points,
+                                lidar_depth_base_sigma_m, lidar_incidence_sigma_scale, depth_var_min_m2,
+                                point_support_n0, point_support_alpha, spread_mad_beta, repr_gamma,
+                                lidar_ray_plane_fit_max_points, plane_intersection_delta,
+                                plane_angle_sigmoid_alpha, plane_angle_sigmoid_t, plane_planarity_sigmoid_beta,
+                                plane_planarity_rho0, plane_residual_exp_gamma, plane_fit_eps, depth_min_m,
+                                depth_sigma_max_sq, depth_min_sigmoid_alpha_z] */
+#define GC_CAM_EV 9          /* per query: Lambda_A theta_A Lambda_B theta_B Lambda_ell theta_ell, then Route
+                                B's z*, sigma^2 and w (NaN, NaN, 0 where Route B does not run) */
+#define GC_CAM_MAX_NEAR 1024 /* in-radius LiDAR points one query can hold */
+/* lidar_depth_evidence (frontend/sensors/lidar_camera_depth_fusion.py:389-442; _project_camera :80-96,
+   Route A :99-164, Route B :242-386, _fit_plane_weighted :207-239): the LiDAR depth evidence of M
+   query pixels d_uv (M, 2) from N points in the camera frame (N, 3). h_intrinsics (host) = [fx, fy,
+   cx, cy]; h_cfg (host) = GC_CAM_CFG_LEN values; d_point_weights (N; may be NULL: uniform) weighs
+   Route B's plane fit. Outputs (device, caller-allocated): d_evidence (M, GC_CAM_EV) and d_counts
+   int32 (M), the number of z > 0 points whose projection lies within the radius of the query. The
+   candidates of a query are taken in ascending point index, the k_use nearest the ray by (distance,
+   index), and every sum runs in a fixed order: the outputs are bitwise reproducible. The call waits
+   once, for the candidate-cap word. GC_ERR_ARG for N outside [0, 2^22], M outside [0, 4096], a
+   radius <= 0, lidar_plane_fit_min_points < 1, lidar_ray_plane_fit_max_points outside [1, 256],
+   non-finite intrinsics or fx, fy = 0, NULL pointers, or a query with more than GC_CAM_MAX_NEAR
+   points within its radius (the outputs are then not to be used; the reference has no such cap). */
+int32_t gc_lidar_depth_evidence(gc_ctx* ctx, int64_t N, const double* d_points_cam, int64_t M, const double* d_uv,
+                                const double* h_intrinsics, const double* h_cfg, const double* d_point_weights,
+                                double* d_evidence, int32_t* d_counts);
+
+/* The camera half of a scan's MeasurementBatch in one call (backend/backend_node.py:1872-1925):
+   the N base-frame points go to the camera frame (p_cam = R^T (p - t), h_R9 row-major and h_t3 on the
+   host; both NULL: the points are in the camera frame already and rows stay there), lidar_depth_evidence
+   runs for the M features' pixels d_uv (M, 2), splat_prep_fused (frontend/sensors/splat_prep.py:37-134)
+   fuses it with each feature's camera depth (d_Lambda_c, d_theta_c (M)) or falls back to the
+   feature's own d_xyz (M, 3) and d_cov_xyz (M, 3, 3), every feature goes to the base frame, and
+   feature_list_to_camera_batch (backend/camera_batch_utils.py:23-86) with
+   measurement_batch_from_camera_splats (backend/structures/measurement_batch.py:165-259) writes rows
+   [0, min(M, n_feat)). d_mu_app (M, 3) is read where d_has_mu_app (uint8, M) is set (else the
+   direction is the row's position), d_color (M, 3) where d_has_color is set (else grey 0.5).
+   Outputs (device, caller-allocated): the nine batch arrays of n_total = n_feat + n_surfel rows as
+   gc_extract_lidar_surfels lays them out, every row from min(M, n_feat) on zero; d_fused_xyz
+   (M, 3), d_fused_cov (M, 3, 3) (camera frame, as splat_prep_fused returns them) and d_fused_flag
+   (uint8, M; 0 = fell back); d_evidence and d_counts as above. One wait, for the candidate-cap word.
+   GC_ERR_ARG as gc_lidar_depth_evidence, and for n_feat or n_surfel outside [0, 2^24] or n_lobes
+   outside [1, 8]. */
+int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_points_base, const double* h_R9,
+                                    const double* h_t3, int64_t M, const double* d_uv, const double* d_Lambda_c,
+                                    const double* d_theta_c, const double* d_weight, const double* d_kappa,
+                                    const double* d_mu_app, const uint8_t* d_has_mu_app, const double* d_color,
+                                    const uint8_t* d_has_color, const double* d_xyz, const double* d_cov_xyz,
+                                    const double* h_intrinsics, const double* h_cfg, double pixel_sigma,
+                                    double timestamp_sec, int32_t n_feat, int32_t n_surfel, int32_t n_lobes,
+                                    double eps_lift, double* d_Lambdas, double* d_thetas, double* d_etas,
+                                    double* d_weights_out, int32_t* d_sources, int32_t* d_source_indices,
+                                    uint8_t* d_valid_mask, double* d_timestamps_out, double* d_colors,
+                                    double* d_fused_xyz, double* d_fused_cov, uint8_t* d_fused_flag,
+                                    double* d_evidence, int32_t* d_counts);
+
+/* measurement_batch_from_camera_splats (backend/structures/measurement_batch.py:165-259): rows
+   [0, min(N, n_feat)) of a fresh batch from positions (N, 3), covariances (N, 3, 3), directions
+   (N, 3), kappas, weights, timestamps (N) and colours (N, 3; may be NULL: grey 0.5), all on the
+   device: Lambda = inv(Sigma + eps_lift I), theta = Lambda mu, eta lobe 0 = kappa d, colours clipped
+   to [0, 1], sources 0, source_indices = row, valid_mask 1; every other row zero. No wait.
+   GC_ERR_ARG for N outside [0, 2^24], budgets as above, or NULL pointers. */
+int32_t gc_measurement_batch_from_camera_splats(gc_ctx* ctx, int64_t N, const double* d_positions,
+                                                const double* d_covariances, const double* d_directions,
+                                                const double* d_kappas, const double* d_weights,
+                                                const double* d_timestamps, const double* d_colors_in,
+                                                int32_t n_feat, int32_t n_surfel, int32_t n_lobes, double eps_lift,
+                                                double* d_Lambdas, double* d_thetas, double* d_etas,
+                                                double* d_weights_out, int32_t* d_sources,
+                                                int32_t* d_source_indices, uint8_t* d_valid_mask,
+                                                double* d_timestamps_out, double* d_colors);
+
 #ifdef __cplusplus
 }
 #endif
