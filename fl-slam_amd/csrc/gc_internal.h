@@ -13,10 +13,7 @@ struct gc_comm;
 namespace gc {
 // a device run hash (gc_runs.h RunTable): 2^bits 8-B entries (>= 2^kRunLoadShift x the rows) and
 // the 2^(bits - kRunLoadShift) position-indexed successor links after them, all zero between uses
-#ifndef GC_RUN_LOAD_SHIFT
-#define GC_RUN_LOAD_SHIFT 2
-#endif
-constexpr uint32_t kRunLoadShift = GC_RUN_LOAD_SHIFT;
+constexpr uint32_t kRunLoadShift = 2;
 // the linear probe (gc_runs.h) relies on a table strictly larger than its runs
 static_assert(kRunLoadShift >= 1, "the run hash needs more entries than rows");
 struct RunTableBuf {

@@ -24,12 +24,6 @@ namespace {
 
 constexpr uint32_t kDropped = 0xFFFFFFFFu;
 
-// the packed record's apply with the sort block's rows staged in LDS (k_fuse_apply_blk), or gathered
-// from HBM by 128-position workgroups (k_fuse_apply)
-#ifndef GC_FUSE_STAGED
-#define GC_FUSE_STAGED 1
-#endif
-
 struct FuseArgs {
   gc_primitive_map map;
   gc_fuse_batch meas;
@@ -129,10 +123,7 @@ GC_DEV void slot_colour(const gc_primitive_map& m, int64_t s, double cam, const 
 // idle (C5 fuse 0.081 -> 0.065 ms, profiles/r04/probe_soft_assign_store_only_and_fuse512.txt). The
 // sort keeps one key per thread in a register (reg_bitonic_sort): 0.062 -> 0.054 ms against the
 // all-LDS network, 256- and 512-row blocks alike (profiles/r04/ab_fuse_regsort.txt)
-#ifndef GC_FUSE_BLK
-#define GC_FUSE_BLK 256
-#endif
-constexpr int kFuseBlk = GC_FUSE_BLK;
+constexpr int kFuseBlk = 256;
 __global__ void __launch_bounds__(kFuseBlk) k_fuse_runs(const int32_t* __restrict__ target, int64_t K, int64_t M,
                                                    RunTable T, uint32_t* sslot, uint32_t* order,
                                                    uint32_t* run_len, uint32_t* rank) {
@@ -256,21 +247,9 @@ GC_DEV void fuse_apply_rec32(const FuseArgs& A, int64_t s, double* rec, const do
     else slot_colour(m, s, rec[16], rec + 18, rec[21], A.eps_mass);
   }
 }
-GC_DEV void fuse_apply_slot32(const FuseArgs& A, int64_t s, const double* d) {
-  typedef double dvec2 __attribute__((ext_vector_type(2)));
-  const dvec2* rp = reinterpret_cast<const dvec2*>((const char*)A.map.Lambdas + s * A.map.slot_bytes);
-  double rec[32];
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const dvec2 x = rp[v];
-    rec[2 * v] = x.x;
-    rec[2 * v + 1] = x.y;
-  }
-  fuse_apply_rec32(A, s, rec, d);
-}
 
 // one thread per sorted position; the owner of each slot (the run its list ends on) fuses the slot
-template <int LT, bool R32>  // R32: the packed 3-lobe record (A.rec32)
+template <int LT>
 __global__ void __launch_bounds__(kApplyWG) k_fuse_apply(FuseArgs A, int64_t K, RunTable T,
                                                     const uint32_t* __restrict__ sslot,
                                                     const uint32_t* __restrict__ order,
@@ -317,8 +296,7 @@ __global__ void __launch_bounds__(kApplyWG) k_fuse_apply(FuseArgs A, int64_t K, 
         add_run(r);
       }
     }
-    if constexpr (R32) fuse_apply_slot32(A, s, d);
-    else fuse_apply_slot<LT>(A, s, d);
+    fuse_apply_slot<LT>(A, s, d);
     if (s1 != 0u) rl.clear();
     T.e[rank[p]] = 0ull;  // the entry and the chain empty for the next call
   }
@@ -345,7 +323,7 @@ constexpr int kStageDoubles = (9 + 3 + 9 + 1 + 1 + 3) * kFuseBlk;
 constexpr size_t kStageLds = sizeof(double) * kStageDoubles + sizeof(int32_t) * kFuseBlk +
                              sizeof(uint32_t) * kFuseBlk * kBlkRunCap;
 // one workgroup's dynamic LDS on gfx950 (160 KiB per CU, all of it addressable by one workgroup once
-// ensure_dyn_lds raises the limit): ~62 KB at GC_FUSE_BLK=256, ~125 KB at 512
+// ensure_dyn_lds raises the limit): ~62 KB at kFuseBlk = 256, ~125 KB at 512
 static_assert(kStageLds <= 160 * 1024, "the staged fuse apply's rows do not fit one workgroup's LDS");
 __global__ void __launch_bounds__(kFuseBlk) k_fuse_apply_blk(FuseArgs A, int64_t K, RunTable T,
                                                          const uint32_t* __restrict__ sslot,
@@ -545,7 +523,9 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
   // scratch: the sorted slot, row order, run length and owner's entry of every position, the apply
   // launch's per-workgroup distinct-slot counts (the run hash and its links are the context's)
   const size_t kv = ((size_t)K * sizeof(uint32_t) + 255) / 256 * 256;
-  const bool staged = A.rec32 && GC_FUSE_STAGED;  // k_fuse_apply_blk: one workgroup per sort block
+  // the packed record's apply with the sort block's rows staged in LDS (k_fuse_apply_blk: one workgroup per
+  // sort block); other layouts gather the rows from HBM by 128-position workgroups (k_fuse_apply)
+  const bool staged = A.rec32;
   const unsigned nblk = (unsigned)((K + kFuseBlk - 1) / kFuseBlk);
   const unsigned grid = staged ? nblk : (unsigned)((K + kApplyWG - 1) / kApplyWG);
   char* base = (char*)scr;
@@ -566,14 +546,11 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
     GC_HIP(ctx, gc::ensure_dyn_lds((const void*)k_fuse_apply_blk, kStageLds));
     hipLaunchKernelGGL(k_fuse_apply_blk, dim3(grid), dim3(kFuseBlk), kStageLds, ctx->stream, A, K, T, sslot, order,
                        run_len, rank, cnt);
-  } else if (A.rec32)
-    hipLaunchKernelGGL((k_fuse_apply<3, true>), dim3(grid), dim3(kApplyWG), 0, ctx->stream, A, K, T, sslot, order,
-                       run_len, rank, cnt);
-  else if (l3)
-    hipLaunchKernelGGL((k_fuse_apply<3, false>), dim3(grid), dim3(kApplyWG), 0, ctx->stream, A, K, T, sslot, order,
+  } else if (l3)
+    hipLaunchKernelGGL(k_fuse_apply<3>, dim3(grid), dim3(kApplyWG), 0, ctx->stream, A, K, T, sslot, order,
                        run_len, rank, cnt);
   else
-    hipLaunchKernelGGL((k_fuse_apply<0, false>), dim3(grid), dim3(kApplyWG), 0, ctx->stream, A, K, T, sslot, order,
+    hipLaunchKernelGGL(k_fuse_apply<0>, dim3(grid), dim3(kApplyWG), 0, ctx->stream, A, K, T, sslot, order,
                        run_len, rank, cnt);
   GC_LAUNCH_CHECK(ctx);
   ctx->runs.dirty = false;  // every entry the runs pass set, its owner cleared

@@ -21,19 +21,9 @@ int32_t cloud_parse_on(gc_ctx* ctx, hipStream_t st, int32_t* flag, const uint8_t
                        uint8_t* d_ring_out, uint8_t* d_tag_out);
 }
 
-// the period (in scans) of the combine_final completion events the slot staging orders on (0: none,
-// every staging that must wait records an event on the compute stream; gc_pipeline::fin_ev)
-#ifndef GC_BIND_EVERY
-#define GC_BIND_EVERY 1
-#endif
-constexpr int64_t kBindEvery = GC_BIND_EVERY;
-
-// the in-scan map update on a stream of its own (1), beside the next scan, or on the compute stream
-// after the combine (0)
-#ifndef GC_SMAP_SIDE
-#define GC_SMAP_SIDE 1
-#endif
-constexpr bool kSmapSide = GC_SMAP_SIDE != 0;
+// the period (in scans) of the combine_final completion events the slot staging orders on
+// (gc_pipeline::fin_ev)
+constexpr int64_t kBindEvery = 1;
 
 struct gc_pipeline {
   gc_ctx* ctx = nullptr;
@@ -104,7 +94,7 @@ struct gc_pipeline {
   double smap_voxel = 0.0;
   bool smap_colors = false;  // the colour pass is due (first update after attaching a map with colours not current)
   gc::ScanMapWork smapW;
-  // With kSmapSide the update runs on mstream, started by combine_final's completion signal
+  // The update runs on a stream of its own (mstream), started by combine_final's completion signal
   // (smap_go, the launch's own: no packet of its own), from the scan's snapshot block of
   // P.smap_snap (snap_base + (ticket & 1) x kSnapLen: the inputs the next scan rewrites, copied by
   // combine_final) and the slot (its restaging waits on `consumed`, recorded after the update). The
@@ -750,7 +740,7 @@ static int32_t scan_finish_impl(gc_pipeline* p, const double* h_gather) {
   hipEvent_t fin = nullptr;
   int fin_e = -1;
   const bool smap = smap_active(p);
-  if (kBindEvery > 0 && !smap && p->pending_ticket > 0 && p->pending_ticket % kBindEvery == 0) {
+  if (!smap && p->pending_ticket > 0 && p->pending_ticket % kBindEvery == 0) {
     fin_e = (int)((p->pending_ticket / kBindEvery) & 1);
     fin = p->fin_ev[fin_e];
     p->fin_ticket[fin_e] = 0;  // the event is re-armed by this launch: unusable until it succeeds
@@ -763,8 +753,7 @@ static int32_t scan_finish_impl(gc_pipeline* p, const double* h_gather) {
     GC_HIP(ctx, hipStreamWaitEvent(ctx->stream, p->smap_done[par], 0));
     p->smap_done_rec[par] = false;
   }
-  const bool side = smap && p->mstream;
-  if (side) fin = p->smap_go;
+  if (smap) fin = p->smap_go;  // starts the update on mstream (created when the map was attached)
   GC_HIP(ctx, gc::launch_combine_final(P, p->pending_S, ctx->stream, fin));
   // only a launch that carries the event makes it cover this ticket (a failed launch leaves it
   // cleared, so slot_wait_consumed falls back to an event recorded on the compute stream)
@@ -777,9 +766,9 @@ static int32_t scan_finish_impl(gc_pipeline* p, const double* h_gather) {
     auto& s = p->slots[p->pending_slot];
     const gc::ScanArgs& S = p->pending_S;
     const gc::ScanMapInput in{s.pts, s.t, s.w, S.t0, S.t1, p->smap_voxel, S.t1, p->pending_seq};
-    hipStream_t ms = side ? p->mstream : ctx->stream;
-    if (side) GC_HIP(ctx, hipStreamWaitEvent(ms, p->smap_go, 0));
-    if (side && ctx->side_pending && ctx->side_ev != p->smap_done[0] && ctx->side_ev != p->smap_done[1]) {
+    hipStream_t ms = p->mstream;
+    GC_HIP(ctx, hipStreamWaitEvent(ms, p->smap_go, 0));
+    if (ctx->side_pending && ctx->side_ev != p->smap_done[0] && ctx->side_ev != p->smap_done[1]) {
       // the context keeps one side event: another pipeline's update is still pending on it, so this
       // update orders after it and the event recorded below covers both (join_side then joins every
       // pipeline's update, not only the last one's)
@@ -804,7 +793,7 @@ static int32_t scan_finish_impl(gc_pipeline* p, const double* h_gather) {
     hipError_t er = hipEventRecord(s.consumed, ms);
     s.consumed_rec = er == hipSuccess;
     s.consumed_ticket = 0;
-    if (side && er == hipSuccess) {
+    if (er == hipSuccess) {
       er = hipEventRecord(p->smap_done[par], ms);
       p->smap_done_rec[par] = er == hipSuccess;
       ctx->side_ev = p->smap_done[par];
@@ -863,7 +852,7 @@ int32_t gc_pipeline_attach_primitive_map(gc_pipeline* p, const gc_primitive_map*
   GC_CHECK_ARG(p->ctx, voxel_m > 0.0, "voxel_m must be positive");
   if (p->mstream) GC_TRY(gc::wait_stream(p->ctx, p->mstream, "the map-update stream before re-attaching"));
   GC_TRY(gc::scan_map_prepare(p->ctx, &p->smapW, p->P.n_cap, map->m_slots));
-  if (kSmapSide && !p->mstream) {
+  if (!p->mstream) {
     // the start signal orders device work only; the done events keep the system-scope release (a
     // host copy of the map joined after them reads memory the update wrote)
     GC_HIP(p->ctx, hipEventCreateWithFlags(&p->smap_go, hipEventDisableTiming | hipEventDisableSystemFence));

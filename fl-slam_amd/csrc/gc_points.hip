@@ -40,10 +40,6 @@ GC_DEV double dpp_f64(double v) {
   const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
   return __hiloint2double(hi, lo);
 }
-template <int CTRL>
-GC_DEV int dpp_i32(int v) {
-  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, false);
-}
 constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
 
 GC_DEV double group16_sum(double v) {
@@ -53,123 +49,8 @@ GC_DEV double group16_sum(double v) {
   v += dpp_f64<kDppMirror>(v);
   return v;
 }
-// The same 16-lane sum for the issue-bound fused bins block, its exchanges on the LDS pipe: each
-// ds_swizzle (bit mode, lane ^ XOR inside 32-lane halves) moves one 32-bit half of the partner's
-// value through the LDS crossbar without touching memory, so a round costs the SIMD one f64 add
-// instead of two DPP moves and an add (the block's VALU slots are its bound; the LDS pipe runs
-// beside them). xor butterfly: lanes a and a ^ k add the same two partials, so all 16 lanes still
-// end with the bit-identical total.
-// GC_ZSUM: 0 = DPP per step (group16_sum), 1 = four swizzle rounds, 2 = two DPP rounds then two swizzle
-// rounds, 3 = a reduce-scatter over four steps at a time (group16_sum4, after recip1), 4 = over two steps
-// (group16_sum2): the default. Same bits in every mode; H = 256 1.1529 -> 1.1336 ms per step with 4,
-// 1.1351 with 3 (whose kernels also spill more), H = 32 no slower (profiles/r07/ab_bins_zbatch.txt).
-// GC_ZSUM_AHEAD: the mode of the look-ahead instantiation of k_bins_io (short tasks), by default the same.
-#ifndef GC_ZSUM
-#define GC_ZSUM 4
-#endif
-#ifndef GC_ZSUM_AHEAD
-#define GC_ZSUM_AHEAD GC_ZSUM
-#endif
-constexpr int kZsumBatched = 3, kZsumBatched2 = 4;
-template <int XOR>
-GC_DEV double swz_f64(double v) {
-  constexpr int pat = (XOR << 10) | 0x1F;  // and_mask 0x1F, or_mask 0, xor_mask XOR
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), pat);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
-  return __hiloint2double(hi, lo);
-}
-template <int MODE>
-GC_DEV double group16_sum_bins(double v) {
-  if constexpr (MODE == 1 || MODE == 2) {
-    if constexpr (MODE == 2) {
-      v += dpp_f64<kDppXor1>(v);
-      v += dpp_f64<kDppXor2>(v);
-    } else {
-      v += swz_f64<1>(v);
-      v += swz_f64<2>(v);
-    }
-    v += swz_f64<4>(v);
-    v += swz_f64<8>(v);
-    return v;
-  } else {
-    return group16_sum(v);
-  }
-}
-GC_DEV double group16_max(double v) {
-  v = fmax(v, dpp_f64<kDppXor1>(v));
-  v = fmax(v, dpp_f64<kDppXor2>(v));
-  v = fmax(v, dpp_f64<kDppHalfMirror>(v));
-  v = fmax(v, dpp_f64<kDppMirror>(v));
-  return v;
-}
-template <int CTRL>
-GC_DEV void argmax_step(double& best, int& bidx) {
-  const double ob = dpp_f64<CTRL>(best);
-  const int oi = dpp_i32<CTRL>(bidx);
-  if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-}
-// (max, lowest index on ties) over the 16 lanes of a row
-GC_DEV void group16_argmax(double& best, int& bidx) {
-  argmax_step<kDppXor1>(best, bidx);
-  argmax_step<kDppXor2>(best, bidx);
-  argmax_step<kDppHalfMirror>(best, bidx);
-  argmax_step<kDppMirror>(best, bidx);
-}
 
-// exp(x) for the softmax arguments x <= ~0 (x = (s - 1)/τ, |s| <= 1): 256-entry 2^(j/256)
-// table in LDS, k = rint(x 256/ln2) by the round-to-integer magic constant (one FMA, k read
-// from the low word), Cody-Waite reduction r = x - k ln2/256 (|r| <= ln2/512), degree-4 Taylor
-// (truncation < 4e-17 relative), ldexp. ~12 f64 ops instead of ocml's general-range exp.
-// Valid for x >= -5.8e6 (k fits in 32 bits; callers clamp).
-constexpr int kExpTab = 256;
-constexpr double kLn2OverTabHi = 0x1.62e42ffp-9;               // ln2/256, 24 trailing zero bits
-constexpr double kLn2OverTabLo = -1.6409824502660487e-13;      // ln2/256 - hi
-constexpr double kTabOverLn2 = 369.3299304675746;              // 256 / ln2
-GC_DEV void exp_table_init(double* T) {  // needs blockDim.x >= 256
-  if (threadIdx.x < kExpTab) T[threadIdx.x] = exp2((double)threadIdx.x / kExpTab);
-}
 constexpr double kRoundMagic = 6755399441055744.0;  // 1.5 * 2^52: fma(y, c, M) - M = rint(y c)
-GC_DEV double exp_neg(double x, const double* T) {
-  const double ks = fma(x, kTabOverLn2, kRoundMagic);  // k = rint(x 256/ln2) in the low word
-  const double kf = ks - kRoundMagic;
-  const int k = __double2loint(ks);
-  const double r = fma(-kf, kLn2OverTabLo, fma(-kf, kLn2OverTabHi, x));
-  double p = fma(r, 1.0 / 24.0, 1.0 / 6.0);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(T[k & (kExpTab - 1)] * p, k >> 8);
-}
-// exp_neg over N independent arguments, phased so the N table reads are in flight together
-// (one LDS round trip per step instead of one per bin). MAGIC: k by the rounding constant (one
-// FMA + one add, k from the low word) instead of mul + rint + cvt; the soft-assign kernel keeps
-// the rint form (its register budget at 3 waves/SIMD is tighter with the extra integer row).
-template <int N, bool MAGIC = true>
-GC_DEV void exp_neg_n(const double (&x)[N], const double* T, double (&out)[N]) {
-  double kf[N], tv[N];
-  int ki[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    if constexpr (MAGIC) {
-      const double ks = fma(x[j], kTabOverLn2, kRoundMagic);
-      kf[j] = ks - kRoundMagic;
-      ki[j] = __double2loint(ks);
-    } else {
-      kf[j] = rint(x[j] * kTabOverLn2);
-      ki[j] = (int)kf[j];
-    }
-    tv[j] = T[ki[j] & (kExpTab - 1)];
-  }
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const double r = fma(-kf[j], kLn2OverTabLo, fma(-kf[j], kLn2OverTabHi, x[j]));
-    double p = fma(r, 1.0 / 24.0, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    out[j] = ldexp(tv[j] * p, ki[j] >> 8);
-  }
-}
 // 1/z for z > 0 in a normal range, one Newton step on the hardware reciprocal (a few ulp; the
 // fused kernel's softmax normaliser, where it is one of ~140 issue slots per step)
 GC_DEV double recip1(double z) {
@@ -184,22 +65,23 @@ GC_DEV double recip(double z) {
   e = fma(-z, r, 1.0);
   return fma(r, e, r);
 }
-// The 16-lane sums of four steps at once, as a reduce-scatter: the butterfly above leaves one number in
-// all 16 lanes of a row and every lane then takes the same reciprocal; here each exchange round halves
-// the values a lane carries, so four steps' sums cost 5 adds and 1 reciprocal instead of 16 and 4.
-//   round 1 (lane bit 0): a lane keeps the step of its own parity of each pair (z0, z1), (z2, z3) and
-//     sends the other to its xor-1 partner: even lanes hold the pair sums of steps 0 and 2, odd lanes
-//     those of steps 1 and 3;
-//   round 2 (lane bit 1): the same on the two results over xor 2. Lane l now holds the quad sum of step
-//     l & 3 (lanes 0, 4, 8, 12: step 0; 1, 5, 9, 13: step 1; 2, 6, 10, 14: step 2; 3, 7, 11, 15: step 3);
+// The 16-lane sums of two steps at once, as a reduce-scatter: the butterfly above leaves one number in
+// all 16 lanes of a row and every lane then takes the same reciprocal; here the first exchange round
+// halves the values a lane carries, so two steps' sums cost 4 adds and 1 reciprocal instead of 8 and 2.
+//   round 1 (lane bit 0): a lane keeps the step of its own parity of the pair (z0, z1) and sends the other
+//     to its xor-1 partner: even lanes hold the pair sums of step 0, odd lanes those of step 1;
+//   round 2: the butterfly's xor 2, which keeps the parity of the lane;
 //   rounds 3, 4: row_shl:4 then row_shl:8 (lane l reads lane l + 4, l + 8 of its row; a source past the
-//     row reads 0): lanes of one class only ever meet their own class, so lane q = 0..3 of each row ends
-//     with step q's total (the row mirrors of group16_sum reverse a quad and would mix the steps). The
-//     other lanes hold partial sums nobody reads.
+//     row reads 0): lanes of one parity only ever meet their own parity, so lanes 0 and 1 of each row end
+//     with the totals of steps 0 and 1 (the row mirrors of group16_sum reverse a quad and would mix the
+//     steps). The other lanes hold partial sums nobody reads.
 // Per step the additions are those of the butterfly in its association, ((l0 + l1) + (l2 + l3)) per
 // quad, then (Q0 + Q1) + (Q2 + Q3), with operands swapped at most: the same bits. One recip1 on the
 // lane's own total, then Z and 1/Z of step s go back to the row's 16 lanes by row_newbcast:s, a 64-bit
 // DPP move each (the only DPP control the f64 pipe of gfx90a and later takes on a 64-bit operand).
+// H = 256 1.1529 -> 1.1336 ms per step against the per-step butterfly, H = 32 no slower; a batch of four
+// steps measured 1.1351 and spilled more (profiles/r07/ab_bins_zbatch.txt). The butterfly's exchanges as
+// ds_swizzle on the LDS pipe measured 15 % slower (profiles/r06/ab_zsum_swizzle.txt).
 constexpr int kDppRowShl4 = 0x104, kDppRowShl8 = 0x108, kDppRowBcast0 = 0x150;
 template <int CTRL>
 GC_DEV double dpp_f64_z(double v) {  // dpp_f64 with 0 for a source lane outside the row
@@ -211,22 +93,6 @@ template <int LANE>
 GC_DEV double row_bcast_f64(double v) {  // lane LANE of the row to its 16 lanes: one v_mov_b64_dpp
   return __builtin_amdgcn_update_dpp(0.0, v, kDppRowBcast0 + LANE, 0xF, 0xF, true);
 }
-GC_DEV void group16_sum4(const double (&z)[4], int lane, double (&Z)[4], double (&rZ)[4]) {
-  const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
-  const double a01 = (b0 ? z[1] : z[0]) + dpp_f64<kDppXor1>(b0 ? z[0] : z[1]);
-  const double a23 = (b0 ? z[3] : z[2]) + dpp_f64<kDppXor1>(b0 ? z[2] : z[3]);
-  double q = (b1 ? a23 : a01) + dpp_f64<kDppXor2>(b1 ? a01 : a23);
-  q += dpp_f64_z<kDppRowShl4>(q);
-  q += dpp_f64_z<kDppRowShl8>(q);
-  const double rq = recip1(q);
-  Z[0] = row_bcast_f64<0>(q); rZ[0] = row_bcast_f64<0>(rq);
-  Z[1] = row_bcast_f64<1>(q); rZ[1] = row_bcast_f64<1>(rq);
-  Z[2] = row_bcast_f64<2>(q); rZ[2] = row_bcast_f64<2>(rq);
-  Z[3] = row_bcast_f64<3>(q); rZ[3] = row_bcast_f64<3>(rq);
-}
-// The same over two steps (GC_ZSUM = 4: half the values held across the exchange): round 1 as above, then
-// a lane carries one value. Round 2 is the butterfly's xor 2, which keeps the parity of the lane;
-// rounds 3 and 4 are the row shifts again. Lanes 0 and 1 of each row end with the totals of steps 0, 1.
 GC_DEV void group16_sum2(const double (&z)[2], int lane, double (&Z)[2], double (&rZ)[2]) {
   const bool b0 = (lane & 1) != 0;
   double q = (b0 ? z[1] : z[0]) + dpp_f64<kDppXor1>(b0 ? z[0] : z[1]);
@@ -282,8 +148,8 @@ GC_DEV double ent_shift(double inv_tau, int B) {
 // 2^(j/2048) with (j << 9) subtracted from its high word, so adding (k << 9) to the high word of
 // T[k & 2047] yields 2^(j/2048)·2^(k >> 11) for any k (one integer add instead of a shift and a
 // v_ldexp). r = y - rint(y) is exact (Sterbenz), |r| <= 1/2, and e^{r ln2/2048} needs only a
-// cubic (truncation (ln2/4096)^4/24 = 3.5e-17). 13 VALU slots per exp with the 3-FMA logit
-// (16 for exp_neg_n). Valid for y in [-2048·700/ln2, 0] (normal results).
+// cubic (truncation (ln2/4096)^4/24 = 3.5e-17). 13 VALU slots per exp with the 3-FMA logit.
+// Valid for y in [-2048·700/ln2, 0] (normal results).
 constexpr int kExpTab2 = 2048;
 constexpr double kTab2OverLn2 = 2954.6394437405970;     // 2048 / ln2
 constexpr double kExp2C1 = 3.3845077175902435e-04;     // ln2 / 2048
@@ -452,29 +318,6 @@ GC_DEV void deskew_point_fast(const double* p, double alpha, const double* xi, d
 // θ² <= 1 — three independent Horner chains instead of sqrt + sincos + two reciprocals. Larger
 // rotations (|α ω| > 1 rad within one scan) take the sincos form.
 constexpr double kInvFact[22] = {1.0, 1.0, 0.5, 0.16666666666666666, 0.041666666666666664, 0.008333333333333333, 0.001388888888888889, 0.0001984126984126984, 2.48015873015873e-05, 2.7557319223985893e-06, 2.755731922398589e-07, 2.505210838544172e-08, 2.08767569878681e-09, 1.6059043836821613e-10, 1.1470745597729725e-11, 7.647163731819816e-13, 4.779477332387385e-14, 2.8114572543455206e-15, 1.5619206968586225e-16, 8.22063524662433e-18, 4.110317623312165e-19, 1.9572941063391263e-20};
-GC_DEV void deskew_point_series(const double* p, double alpha, const double* xi, double* out) {
-  const double phi[3] = {alpha * xi[3], alpha * xi[4], alpha * xi[5]};
-  const double ts = dot3(phi, phi);
-  if (ts > 1.0) {
-    deskew_point_fast(p, alpha, xi, out);
-    return;
-  }
-  const double rho[3] = {alpha * xi[0], alpha * xi[1], alpha * xi[2]};
-  const double u = -ts;
-  double a = kInvFact[19], Bv = kInvFact[20], Cv = kInvFact[21];
-#pragma unroll
-  for (int k = 8; k >= 0; --k) {
-    a = fma(a, u, kInvFact[2 * k + 1]);
-    Bv = fma(Bv, u, kInvFact[2 * k + 2]);
-    Cv = fma(Cv, u, kInvFact[2 * k + 3]);
-  }
-  double V[9], R[9], t[3], q[3];
-  rodrigues_form(phi, Bv, Cv, V);
-  mat3_vec(V, rho, t);
-  rodrigues_form(phi, a, Bv, R);
-  q[0] = p[0] - t[0]; q[1] = p[1] - t[1]; q[2] = p[2] - t[2];
-  mat3_tvec(R, q, out);
-}
 // Fused-kernel deskew in cross-product form: V ρ = ρ + B φ×ρ + C φ×(φ×ρ) and Rᵀ q = q − a φ×q + B φ×(φ×q)
 // (the same Rodrigues matrices applied as vectors: 4 cross products instead of two 3x3 forms and two
 // matrix-vector products). SHORT: the series for θ² <= kDeskewShortTs (six terms, first omitted term
@@ -526,17 +369,6 @@ GC_DEV void direction_fast(const double* p, const double* o, double eps, double*
   const double inv = recip(sqrt(r0 * r0 + r1 * r1 + r2 * r2) + eps);
   d[0] = r0 * inv; d[1] = r1 * inv; d[2] = r2 * inv;
 }
-// σ(x) = 1 / (1 + e^{-x}) from e = exp(-|x|) (table exp; arguments below -745 underflow to 0)
-GC_DEV double sigmoid_fast(double x, const double* T) {
-  const double e = exp_neg(fmax(-fabs(x), -800.0), T);
-  const double r = recip(1.0 + e);
-  return x >= 0.0 ? r : e * r;
-}
-GC_DEV double window_weight_fast(double t, double t0, double t1, double inv_sig, const double* T) {
-  const double wr = sigmoid_fast((t - t0) * inv_sig, T) * sigmoid_fast((t1 - t) * inv_sig, T);
-  return wr * (1.0 - 1e-12) + 1e-12;
-}
-
 GC_DEV double window_weight2(double t, double t0, double t1, double inv_sig, const double* T) {
   const double wr = sigmoid2((t - t0) * inv_sig, T) * sigmoid2((t1 - t) * inv_sig, T);
   return wr * (1.0 - 1e-12) + 1e-12;
@@ -676,13 +508,9 @@ GC_DEV void sa_store_block(const double* S, double* Rh, int64_t wbase, int64_t n
 // (at 3, the 168-VGPR budget spilled ~12-27 VGPRs per point to scratch: 0.6 GB of extra HBM reads and
 // 0.9 GB of extra writes per C3 launch, tools/probe/probe_sa3.hip; 1.74 -> 1.32 ms)
 constexpr int kSaOcc = 2;
-// the responsibility rows' store kind (A/B builds): 0 non-temporal (default), 1 plain, 2 sc1 write-through
-// by inline asm. sc1 took the kernel 1.39 -> 1.33 ms (5.15 TB/s, 90 % of the plain-write probe) and the
-// pair 0.673 -> 0.676 (profiles/r05/ab_soft_assign_store_and_moment_order.txt), but its asm form wrote
-// wrong values on a ragged tail (test_soft_assign_matches_oracle[32-333]): not adopted
-#ifndef GC_SA_STORE
-#define GC_SA_STORE 0
-#endif
+// the responsibility rows leave by non-temporal stores: plain stores and an inline-asm sc1 write-through were
+// tried, sc1 taking the kernel 1.39 -> 1.33 ms (the soft-assign / moment pair's roofline fraction 0.673 ->
+// 0.676) but writing wrong values on a ragged tail (profiles/r05/ab_soft_assign_store_and_moment_order.txt)
 // dynamic LDS of a soft-assign workgroup (doubles): exp table | bins (x, y, z rows of 64) | reduction |
 // 4 wave slabs (FULL: 32 rows of 16 BPL + 2; ragged: 64 rows of 18)
 __host__ __device__ constexpr bool sa_linear(int BPL, bool full) { return full && BPL <= 3; }  // B = 64: 16-bin blocks (register budget)
@@ -806,13 +634,7 @@ __global__ void __launch_bounds__(256, kSaOcc) k_soft_assign(int64_t n, int B, i
         const int64_t pbase = wbase + 32 * hf;
         double* dst = Rh + pbase * NB;
         const auto put = [&](int o, const dvec2& v) {
-#if GC_SA_STORE == 1
-          *reinterpret_cast<dvec2*>(dst + o) = v;  // plain
-#elif GC_SA_STORE == 2
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst + o), "v"(v) : "memory");  // write-through
-#else
           __builtin_nontemporal_store(v, reinterpret_cast<dvec2*>(dst + o));
-#endif
         };
         if (pbase + 32 <= n) {  // wave-uniform: the whole block is in range (every block but the tail's)
 #pragma unroll
@@ -883,18 +705,12 @@ __global__ void k_soft_assign_finalize(const double* __restrict__ partial, int64
 // of its use (register double buffer, ~12 KiB of responsibilities in flight per wave); no LDS
 // round trip. Features are computed lane = point for the next group and handed over through a
 // wave-private LDS slab (feature-major, stride 34: the B-operand reads are bank-conflict free).
-// NACC = 2: even and odd steps accumulate into separate tiles (2*BPL*NT independent MFMA chains)
-// added in the epilogue. The 4 waves are reduced in a fixed order into one record per chunk.
+// The 4 waves are reduced in a fixed order into one record per chunk.
 constexpr int kMomFS = 34;
 // PAIR (B >= 32, 16-B aligned rows): bins 0..31 arrive as one 16-B load per lane (bins 2l, 2l+1 of its
 // point: four 256-B row segments per load instead of two loads of four 128-B segments); tile 0 holds
 // the even bins, tile 1 the odd ones (row i of tile j < 2 is bin 2i + j), tiles >= 2 bins 16j + l.
-#ifndef GC_MOM_FORWARD
-constexpr bool kMomReverse = true;
-#else
-constexpr bool kMomReverse = false;
-#endif
-template <int BPL, bool COV, bool LAM, int NACC, bool PAIR>
+template <int BPL, bool COV, bool LAM, bool PAIR>
 __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, int groups,
                                                            const double* __restrict__ pts,
                                                            const double* __restrict__ covs,
@@ -907,9 +723,10 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
   extern __shared__ double lds[];
   // workgroups run the (hypothesis, chunk) grid from its end: the soft-assign before this kernel wrote
   // the responsibilities in ascending block order, so the last-written (still in the Infinity Cache /
-  // L2) are read first (records, and so the sums, are the same in either order)
-  const int bx = kMomReverse ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
-  const int h = kMomReverse ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y;
+  // L2) are read first (records, and so the sums, are the same in either order; the forward order measured
+  // the same, profiles/r05/ab_soft_assign_store_and_moment_order.txt)
+  const int bx = (int)(gridDim.x - 1 - blockIdx.x);
+  const int h = (int)(gridDim.y - 1 - blockIdx.y);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, bl = lane & 15;
   double* F = lds + wv * (16 * NT * kMomFS);
   const double o[3] = {o0, o1, o2};
@@ -918,13 +735,11 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
   int64_t wend = wbeg + (int64_t)groups * 32;
   wend = wend < n ? wend : n;
   const int ng = wbeg < n ? (int)((wend - wbeg + 31) / 32) : 0;
-  v4d acc[NACC][BPL][NT];
+  v4d acc[BPL][NT];
 #pragma unroll
-  for (int e = 0; e < NACC; ++e)
+  for (int j = 0; j < BPL; ++j)
 #pragma unroll
-    for (int j = 0; j < BPL; ++j)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[e][j][t] = v4d{0.0, 0.0, 0.0, 0.0};
+    for (int t = 0; t < NT; ++t) acc[j][t] = v4d{0.0, 0.0, 0.0, 0.0};
   // this lane's responsibility column offsets (bins 16 j + l), clamped into the row
   int cb[BPL];
   bool cv[BPL];
@@ -994,7 +809,7 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
       _Pragma("unroll") for (int j_ = 0; j_ < BPL; ++j_) {                      \
         const double ra_ = cv[j_] ? RR[s_][j_] : 0.0;                           \
         _Pragma("unroll") for (int t_ = 0; t_ < NT; ++t_)                       \
-          acc[s_ % NACC][j_][t_] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra_, fb_[t_], acc[s_ % NACC][j_][t_], 0, 0, 0); \
+          acc[j_][t_] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra_, fb_[t_], acc[j_][t_], 0, 0, 0);         \
       }                                                                         \
     }                                                                           \
   }
@@ -1028,7 +843,7 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
 #undef GC_LOAD_RAW
 #undef GC_FEATURES
 #undef GC_CONSUME
-  // epilogue: even + odd tiles, then the 4 waves in a fixed order (LDS reused)
+  // epilogue: the 4 waves in a fixed order (LDS reused)
   __syncthreads();
   double* red = lds;  // [4][B][NF]
 #pragma unroll
@@ -1038,7 +853,7 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int b = (PAIR && j < 2) ? 2 * (g + 4 * r) + j : 16 * j + g + 4 * r, k = 16 * t + bl;  // D[row g + 4r][col l]
-        if (b < B && k < NF) red[(wv * B + b) * NF + k] = NACC == 2 ? acc[0][j][t][r] + acc[NACC - 1][j][t][r] : acc[0][j][t][r];
+        if (b < B && k < NF) red[(wv * B + b) * NF + k] = acc[j][t][r];
       }
   __syncthreads();
   int64_t npts = n - (int64_t)bx * 4 * groups * 32;
@@ -1060,22 +875,6 @@ __global__ void __launch_bounds__(256, 2) k_moment_partials(int64_t n, int B, in
 struct NoHook {
   GC_DEV void operator()() const {}
 };
-// v + v^16 then + v^32 over the lane index (the value of lane l's column summed over the wave's four
-// 16-lane rows) by gfx950's row and half swaps on the VALU instead of two LDS-routed shuffles; each
-// step adds a lane pair in one order or the other, which is the same double (x + y == y + x)
-GC_DEV double sum_rows4(double v) {
-  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
-  const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  const double w = __hiloint2double(h16[0], l16[0]) + __hiloint2double(h16[1], l16[1]);
-  const unsigned wl = __double2loint(w), wh = __double2hiint(w);
-  const auto l32 = __builtin_amdgcn_permlane32_swap(wl, wl, false, false);
-  const auto h32 = __builtin_amdgcn_permlane32_swap(wh, wh, false, false);
-  return __hiloint2double(h32[0], l32[0]) + __hiloint2double(h32[1], l32[1]);
-}
-#ifndef GC_EPI_PERMLANE
-#define GC_EPI_PERMLANE 0
-#endif
 GC_DEV int64_t uniform_i64(int64_t v) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
   const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)v >> 32));
@@ -1102,14 +901,12 @@ GC_DEV void write_partial_record_mfma(const v4d (&acc4)[BPL], double (&accx)[BPL
   for (int j = 0; j < BPL; ++j)
 #pragma unroll
     for (int t = 0; t < NX; ++t) {
-#if GC_EPI_PERMLANE
-      accx[j][t] = sum_rows4(accx[j][t]);
-#else
+      // the column's sum over the wave's four 16-lane rows; gfx950's v_permlane16/32_swap in place of the two
+      // shuffles buys nothing (profiles/r06/ab_bins_epilogue.txt)
       double v = accx[j][t];
       v += __shfl_xor(v, 16, 64);
       v += __shfl_xor(v, 32, 64);
       accx[j][t] = v;
-#endif
     }
   const double e = wave_sum(ent), m = wave_max(mxr), s = wave_sum(sumw);
   double* W = lds + wv * WS;
@@ -1216,42 +1013,20 @@ struct FusedArgs {
   int iters_t;
 };
 constexpr int kFusedNS = NF_BASE + 4;  // feature slab rows: 19 features + d(3) + valid flag
-// Point-major softmax (GC_BINS_LP = 1, B <= 48; off: the A/B in profiles/r06/ab_bins_point_major.txt
-// measured it neutral at H = 256 and 10 % slower at H = 32). The exp / softmax half runs with a quad of
-// lanes per point (12 of its bins per lane, the quad's Z by two DPP rounds instead of the 16-lane
-// butterfly), the responsibilities reach the matrix-core layout through a per-wave LDS slab of 16 points
-// x B, and the moment half is bins_task's. ~14 % fewer VALU slots per block, but a slab round trip and
-// a direction shuffle per 16 points on the chain. Per wave: 18 feature rows (the trace-complement
-// feature DF has no row) of kFusedFS and the 16-row slab of stride 16 BPL + 2; the table after the four
-// waves; no scaled-bins block (each lane holds its 12 bin directions).
-#ifndef GC_BINS_LP
-#define GC_BINS_LP 0
-#endif
-__host__ __device__ constexpr bool bins_lp(int BPL) { return GC_BINS_LP && BPL <= 3; }
-constexpr int kLpFRows = NF_BASE - 1;
-__host__ __device__ constexpr int lp_es(int BPL) { return 16 * BPL + 2; }
-__host__ __device__ constexpr int lp_wave_doubles(int BPL) { return kLpFRows * kFusedFS + 16 * lp_es(BPL); }
-__host__ __device__ constexpr int fused_tab_offset(int BPL) {
-  return bins_lp(BPL) ? 4 * lp_wave_doubles(BPL) : 4 * kFusedFS * kFusedNS;
-}
-// dynamic LDS of a fused workgroup (doubles): 4 wave slabs | exp table | scaled bins (not LP) | epilogue
-// reduction (aliases the slabs). LP at B = 48: 80,000 B, two workgroups per CU.
+// the exp table's offset in a fused workgroup's dynamic LDS (doubles), after the 4 wave slabs. A point-major
+// softmax (a quad of lanes per point, the responsibilities through a per-wave LDS slab into the matrix-core
+// layout) measured neutral at H = 256 and 10 % slower at H = 32 (profiles/r06/ab_bins_point_major.txt).
+__host__ __device__ constexpr int fused_tab_offset() { return 4 * kFusedFS * kFusedNS; }
+// dynamic LDS of a fused workgroup (doubles): 4 wave slabs | exp table | scaled bins | epilogue reduction
+// (aliases the slabs)
 __host__ __device__ inline size_t fused_lds_doubles(int B) {
-  const int bpl = (B + 15) / 16;
-  const size_t a = (size_t)fused_tab_offset(bpl) + kExpTab2 + (bins_lp(bpl) ? 0 : 192),
-               b = 4 * (size_t)B * NF_BASE + 12;
+  const size_t a = (size_t)fused_tab_offset() + kExpTab2 + 192, b = 4 * (size_t)B * NF_BASE + 12;
   return a > b ? a : b;
 }
-static_assert(4 * lp_wave_doubles(3) + kExpTab2 + 1 <= 81920 / 8, "LP bins workgroup beyond half a CU's LDS");
 
-template <int BPL>
 GC_DEV void bins_prologue(const FusedArgs& A, double* lds) {
-  double* Tx = lds + fused_tab_offset(BPL);
+  double* Tx = lds + fused_tab_offset();
   exp_table2_load(Tx);
-  if constexpr (bins_lp(BPL)) {
-    __syncthreads();
-    return;
-  }
   double* Lb = Tx + kExpTab2;  // bin directions pre-scaled by 2048/(τ ln2) (x, y, z rows of 64)
   const double ysc = A.inv_tau * kTab2OverLn2;
   if (threadIdx.x < 64) {
@@ -1315,220 +1090,6 @@ __device__ double g_task_ep[2 * 16384];  // per task [end of its first iteration
 __device__ double g_task_wv[4 * 16384];  // per task and wave: the end of its iterations
 #define GC_BT_NOW() ((double)__builtin_amdgcn_s_memrealtime())
 #endif
-// bins_task in the point-major softmax form (bins_lp): the same task, records and ticket protocol.
-// Per iteration of 64 points per wave:
-//  phase A (lane = point): budget selection, deskew, direction, window weight and the 18 features,
-//     as bins_task;
-//  four sub-iterations of 16 points, lane = (point l >> 2, bin quarter l & 3):
-//   B1: the lane's 12 logits against its bin directions (registers), exps (the 2048-entry table), the
-//       quad's Z by two DPP rounds, 1/Z by one Newton step, Σ R x and max R, r = e / Z into the slab;
-//   B2 (lanes = 4 points x 16 bins): the sub-iteration's 4 steps of BPL MFMAs (A = r of point 4s + g,
-//       bin 16 j + l, from the slab; B = feature l of that point) and the two VALU features.
-template <int BPL, bool FULL, bool PRE>
-GC_DEV void bins_task_lp(const FusedArgs& A, int h, int64_t c, double* lds, double* rec, unsigned* ctr,
-                         unsigned* task_slot, TaskAhead* ahead, unsigned T, int Hl, unsigned* late_next,
-                         int64_t n_sel, int64_t stride) {
-  typedef double dvec2 __attribute__((ext_vector_type(2)));
-  constexpr int NF = NF_BASE;
-  constexpr int DF = 9;
-  constexpr int NX = NF - 16 - 1;
-  constexpr int NB = 16 * BPL, ES = lp_es(BPL), WD = lp_wave_doubles(BPL);
-  constexpr unsigned TAB = 8u * (unsigned)fused_tab_offset(BPL);
-  constexpr int FS = kFusedFS;
-  const int64_t n_cap = A.n_cap;
-  const int B = A.B;
-  int iters;
-  const int64_t chunk0 = chunk_first(A, c, &iters);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int g = lane >> 4, bl = lane & 15;
-  double* F = lds + wv * WD;         // feature rows (row r = feature r, r + 1 past DF) x 64 points
-  double* E = F + kLpFRows * FS;     // exp slab: 16 points x ES
-  const double o[3] = {A.o0, A.o1, A.o2};
-  TaskAhead ta_local;
-  TaskAhead& ta = ahead ? *ahead : ta_local;
-  if (!ahead || !ahead->valid) task_operands<PRE>(A, h, c, n_sel, stride, ta);
-  double xr[6];  // the hypothesis's twist: wave-uniform, held in SGPRs
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const double v = ta.xr[k];
-    xr[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
-                             __builtin_amdgcn_readfirstlane(__double2loint(v)));
-  }
-  const double* __restrict__ pts_raw = A.pts_raw;
-  const double* __restrict__ t_raw = A.t_raw;
-  const double* __restrict__ w_raw = A.w_raw;
-  const double t0 = A.t0, t1 = A.t1;
-  const double scale = A.bscal[2];
-  const double denom = fmax(t1 - t0, 1e-12);
-  const double inv_denom = 1.0 / denom;
-  const double inv_sig = 1.0 / fmax(0.1 * denom, 1e-6);
-  double* Tx = lds + fused_tab_offset(BPL);
-  const double ysc = A.inv_tau * kTab2OverLn2;
-  constexpr int NACC = 1;  // BPL independent MFMA chains per step suffice here (the slab round trip paces them)
-  v4d acc4[NACC][BPL];
-  double accx[BPL][NX];
-#pragma unroll
-  for (int j = 0; j < BPL; ++j) {
-    acc4[0][j] = v4d{0.0, 0.0, 0.0, 0.0};
-    acc4[NACC - 1][j] = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int t = 0; t < NX; ++t) accx[j][t] = 0.0;
-  }
-  double sumw = 0.0, entq = 0.0, mxr = 0.0;
-  double zst = 1.0;  // Π Z of the lane's points as mantissa x 2^zex (renormalised every iteration)
-  int zex = 0;
-  // x = (ysc d)·b <= ysc (1 + 1e-16) < ymax: the exp argument x - ymax <= 0, the shift riding in the
-  // rounding constant (exp2s_shift_tab_n) and added back to the entropy below
-  const double ymax = ceil(ysc);
-  const double Mp = kRoundMagic - ymax;
-  const double Beps = (double)B * 1e-12;
-  double np[3] = {0.0, 0.0, 0.0}, ntt = 0.0, nww = 0.0;
-  auto fetch = [&](int it2) {
-    const int64_t j = chunk0 + (int64_t)it2 * 256 + wv * 64 + lane;
-    np[0] = 0.0; np[1] = 0.0; np[2] = 0.0; ntt = 0.0; nww = 0.0;
-    if (j < n_cap && j < n_sel) {
-      const int64_t i = j * stride;
-      np[0] = pts_raw[3 * i]; np[1] = pts_raw[3 * i + 1]; np[2] = pts_raw[3 * i + 2];
-      ntt = t_raw[i];
-      nww = PRE ? A.w_win[j] : w_raw[i];
-    }
-  };
-  {
-    const bool ok = ta.ok;  // applied here, a task after the loads were issued
-    np[0] = ok ? ta.np[0] : 0.0; np[1] = ok ? ta.np[1] : 0.0; np[2] = ok ? ta.np[2] : 0.0;
-    ntt = ok ? ta.ntt : 0.0; nww = ok ? ta.nww : 0.0;
-  }
-  unsigned next = 0;
-  // this lane's bin set for the quad form: bins NQ c .. NQ c + NQ - 1 (c = lane & 3), pre-scaled by
-  // ysc, in registers for the whole task (ragged B: the bins past B read as bin B - 1, masked below)
-  constexpr int NQ = NB / 4;
-  const int cq = lane & 3;
-  double bq[NQ][3];
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) {
-    const int b = min(NQ * cq + k, B - 1);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) bq[k][r] = A.bins[3 * b + r] * ysc;
-  }
-  auto run_iters = [&](auto pad_tag) {
-    constexpr bool PAD = decltype(pad_tag)::value;
-    for (int it = 0; it < iters; ++it) {
-      const int64_t wbase = chunk0 + (int64_t)it * 256 + wv * 64;
-      if (ctr && !late_next && it == iters - 1 && threadIdx.x == 0) next = atomicAdd(ctr, 1u);
-      // ---- phase A (lane = point): the point's features (w folded in) into the wave's feature rows
-      double d[3];
-      {
-        const bool inr = !PAD || wbase + lane < n_cap;
-        double p[3] = {np[0], np[1], np[2]};
-        const double tt = ntt, ww = nww * scale;
-        if (it + 1 < iters) fetch(it + 1);
-        const double al = (tt - t0) * inv_denom;
-        const double ph[3] = {al * xr[3], al * xr[4], al * xr[5]};
-        double q[3];
-        if (__all(dot3(ph, ph) <= kDeskewShortTs)) deskew_point_cross<true>(p, al, xr, q);
-        else deskew_point_cross<false>(p, al, xr, q);
-        const double wd = inr ? (PRE ? ww : ww * window_weight2(tt, t0, t1, inv_sig, Tx)) : 0.0;
-        direction_fast(q, o, 1e-12, d);
-        sumw += wd;
-        double f[NF];
-        point_features_w(q, d, wd, f);
-#pragma unroll
-        for (int k = 0; k < NF; ++k)
-          if (k != DF) F[(k < DF ? k : k - 1) * FS + lane] = f[k];
-      }
-      // ---- four sub-iterations of 16 points: B1 with lane = (point p = l >> 2, bin quarter c = l & 3),
-      // then B2 over the sub-iteration's 4 MFMA steps
-#pragma unroll
-      for (int sk = 0; sk < 4; ++sk) {
-        const int pt = 16 * sk + (lane >> 2);  // the wave's point (its phase-A lane)
-        const double dx = __shfl(d[0], pt), dy = __shfl(d[1], pt), dz = __shfl(d[2], pt);
-        const double vf = (!PAD || wbase + pt < n_cap) ? 1.0 : 0.0;  // padding: no entropy / max / Π Z
-        // B1: this lane's NQ logits, exps and partial Z, Σ e x, max e (groups of 4: all NQ table reads in
-        // flight at once measured slower, profiles/r06/ab_bins_point_major.txt)
-        double e[NQ];
-        double Zl = 0.0, sl = 0.0, em = 0.0;
-#pragma unroll
-        for (int k0 = 0; k0 < NQ; k0 += 4) {
-          double x[4], ex[4];
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int k = k0 + kk;
-            x[kk] = fma(dz, bq[k][2], fma(dy, bq[k][1], dx * bq[k][0]));
-          }
-          exp2s_shift_tab_n<4, TAB>(x, Mp, ex);
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const int k = k0 + kk;
-            e[k] = (FULL || NQ * cq + k < B) ? ex[kk] : 0.0;
-            Zl += e[k];
-            sl = fma(e[k], x[kk], sl);
-            em = fmax(em, e[k]);
-          }
-        }
-        // Z over the point's quad (two DPP rounds: the four lanes end bit-identical)
-        double Z = Zl + dpp_f64<kDppXor1>(Zl);
-        Z = Z + dpp_f64<kDppXor2>(Z);
-        const double rZ = recip1(Z);
-        entq = fma(sl * rZ, vf, entq);  // this lane's share of Σ R x
-        mxr = fmax(mxr, em * rZ * vf);
-        if (cq == 0) zst *= PAD ? fma(Z - 1.0, vf, 1.0) : Z;  // Π Z once per point
-        // the responsibilities into the exp slab: row = the point within the sub-iteration
-        {
-          double* er = E + (lane >> 2) * ES + NQ * cq;
-#pragma unroll
-          for (int k = 0; k < NQ; k += 2) *reinterpret_cast<dvec2*>(er + k) = dvec2{e[k] * rZ, e[k + 1] * rZ};
-        }
-        lds_wave_sync();
-        // B2 (lanes = 4 points x 16 bins): the sub-iteration's 4 MFMA steps
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int ss = 4 * sk + s;
-          const int pl = 4 * ss + g;
-          const double fb = F[bl * FS + pl];
-          double fk[NX];
-#pragma unroll
-          for (int t = 0; t < NX; ++t) fk[t] = F[(16 + t) * FS + pl];
-#pragma unroll
-          for (int j = 0; j < BPL; ++j) {
-            const double a = E[(4 * s + g) * ES + 16 * j + bl];
-            acc4[ss % NACC][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, fb, acc4[ss % NACC][j], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NX; ++t) accx[j][t] = fma(a, fk[t], accx[j][t]);
-          }
-        }
-        lds_wave_sync();
-      }
-      int e8;
-      zst = frexp(zst, &e8);
-      zex += e8;
-    }
-  };
-  if (chunk0 + (int64_t)iters * 256 <= n_cap) run_iters(std::false_type{});
-  else run_iters(std::true_type{});
-  int64_t npts = n_cap - chunk0;
-  npts = npts < 0 ? 0 : (npts > (int64_t)iters * 256 ? (int64_t)iters * 256 : npts);
-  // entropy over the chunk's valid points: Σ log Z' - Σ R x (x in units of ln2 / 2048) + ymax per valid
-  // point - B ε per point; every lane holds its own points' Π Z (lane 0 of each wave adds the constants)
-  const double logacc = log_pos(zst) + (double)zex * 0.69314718055994530942;
-  const double ent = logacc - entq * kExp2C1 + ((lane == 0) ? (ymax * kExp2C1 - Beps) * (double)npts * 0.25 : 0.0);
-#pragma unroll
-  for (int j = 0; j < BPL; ++j)
-    if (NACC == 2) acc4[0][j] += acc4[NACC - 1][j];
-  if (ahead) ahead->valid = false;
-  if (ctr && late_next && threadIdx.x == 0) *late_next = atomicAdd(ctr, 1u);
-  const auto pre = [&]() {
-    if (ctr && !late_next && threadIdx.x == 0) *task_slot = next;
-  };
-  const auto mid = [&]() {
-    if (!ctr || late_next) return;
-    const unsigned tn = *task_slot;
-    ahead->t = tn;
-    if (tn < T) task_operands<PRE>(A, (int)(tn % (unsigned)Hl), (int64_t)(tn / (unsigned)Hl), n_sel, stride, *ahead);
-  };
-  write_partial_record_mfma<BPL, NX, DF, FULL, WD>(acc4[0], accx, ent, mxr, sumw, (double)npts, B, lds, rec, pre, mid);
-  __syncthreads();
-}
-
 // One task: hypothesis h, chunk c (its points: the tiers of FusedArgs) of the budgeted scan,
 // its partial record written to rec. Ends with the workgroup synchronised (LDS free for the next task).
 // Persistent form (ctr, task_slot, ahead non-null): the next task's ticket is taken by thread 0 at the
@@ -1538,22 +1099,17 @@ GC_DEV void bins_task_lp(const FusedArgs& A, int h, int64_t c, double* lds, doub
 // n_sel, stride: the launch's selection (selection_of), always given by the caller. The non-look-ahead
 // persistent form measured better with it left in vector registers than moved to scalar ones (H = 256
 // 1.1568 against 1.1592 ms; profiles/r06/ab_bins_epilogue.txt).
-// ZMODE: the softmax normaliser's 16-lane sum (GC_ZSUM); the batched modes run the steps four or two at a
-// time.
-template <int BPL, bool FULL, bool PRE, int ZMODE>
+template <int BPL, bool FULL, bool PRE>
 GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double* rec, unsigned* ctr,
                       unsigned* task_slot, TaskAhead* ahead, unsigned T, int Hl, unsigned* late_next, int bt_task,
                       int64_t n_sel, int64_t stride) {
   (void)bt_task;
-  // B = 16 (one bin per lane, every lane full) keeps the per-step sum: its lane partial is a bare
-  // product t p, which the compiler fuses into the butterfly's first add (Z starts as fma(t, p, partner));
-  // the batched first round adds a selected value, which would round the product first: other bits
-  constexpr int ZB = FULL && BPL == 1 ? 1 : ZMODE == kZsumBatched ? 4 : ZMODE == kZsumBatched2 ? 2 : 1;
+  // softmax steps per 16-lane sum and reciprocal (group16_sum2). B = 16 (one bin per lane, every lane full)
+  // keeps the per-step sum: its lane partial is a bare product t p, which the compiler fuses into the
+  // butterfly's first add (Z starts as fma(t, p, partner)); the batched first round adds a selected value,
+  // which would round the product first: other bits
+  constexpr int ZB = FULL && BPL == 1 ? 1 : 2;
   static_assert(kFusedUnr % ZB == 0, "the unrolled block holds whole batches");
-  if constexpr (bins_lp(BPL)) {
-    bins_task_lp<BPL, FULL, PRE>(A, h, c, lds, rec, ctr, task_slot, ahead, T, Hl, late_next, n_sel, stride);
-    return;
-  }
   constexpr int NF = NF_BASE;
   // features 0..8 and 10..16 on the matrix core, 17..18 on the VALU; feature 9 (w d_z²) is the trace
   // complement N − w d_x² − w d_y² (write_partial_record_mfma<.., 9>): one VALU feature fewer per step
@@ -1664,10 +1220,10 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
       }
       lds_wave_sync();
       for (int s8 = 0; s8 < 16; s8 += kFusedUnr) {
-        // Per step (GC_ZSUM 0..2, and B = 16): logits, exps, the 16-lane sum Z and 1/Z, responsibilities,
-        // moments. Kept as it was beside the batched form below, so that these modes compile to the
-        // kernels they were measured as: the block's schedule follows the order of the source, and the same
-        // statements arranged as a batch of one ran 1 % slower at H = 32 (profiles/r07/ab_bins_zbatch.txt)
+        // Per step (B = 16): logits, exps, the 16-lane sum Z and 1/Z, responsibilities, moments. Kept as
+        // its own block beside the batched form below: the block's schedule follows the order of the source,
+        // and the same statements arranged as a batch of one ran 1 % slower at H = 32
+        // (profiles/r07/ab_bins_zbatch.txt)
         if constexpr (ZB == 1) {
   #pragma unroll
       for (int s = s8; s < s8 + kFusedUnr; ++s) {
@@ -1687,7 +1243,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         double zl = e[0];
   #pragma unroll
         for (int j = 1; j < BPL; ++j) zl += e[j];
-        const double Z = group16_sum_bins<ZMODE>(zl);
+        const double Z = group16_sum(zl);
         const double rZ = recip1(Z);
         double r[BPL];
   #pragma unroll
@@ -1713,9 +1269,9 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         }
       }
         } else {
-        // ZB steps at a time: their logits, exps and in-lane sums, then the 16-lane sums and one reciprocal
-        // (group16_sum4 / group16_sum2), then each step's responsibilities and moments in step order and
-        // with the per-step form's expressions
+        // Two steps at a time: their logits, exps and in-lane sums, then the 16-lane sums and one reciprocal
+        // (group16_sum2), then each step's responsibilities and moments in step order and with the per-step
+        // form's expressions
   #pragma unroll
       for (int sb = s8; sb < s8 + kFusedUnr; sb += ZB) {
         double e[ZB][BPL], x[ZB][BPL], zl[ZB], Z[ZB], rZ[ZB];
@@ -1748,8 +1304,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
             for (int j = 1; j < BPL; ++j) zl[u] += e[u][j];
           }
         }
-        if constexpr (ZB == 4) group16_sum4(zl, lane, Z, rZ);
-        else group16_sum2(zl, lane, Z, rZ);
+        group16_sum2(zl, lane, Z, rZ);
   #pragma unroll
         for (int u = 0; u < ZB; ++u) {
           const int s = sb + u;
@@ -1854,7 +1409,7 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_io(FusedArgs A, PipeDev
 #endif
     return;
   }
-  bins_prologue<BPL>(A, lds);
+  bins_prologue(A, lds);
 #ifdef GC_BINS_TIMING
   bt1 = GC_BT_NOW();
 #endif
@@ -1891,12 +1446,12 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_io(FusedArgs A, PipeDev
     const double tt0 = GC_BT_NOW();
 #endif
     if constexpr (AHEAD) {
-      bins_task<BPL, FULL, true, GC_ZSUM_AHEAD>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s,
-                                                &ahead, T, H, nullptr, (int)t, n_sel, stride);
+      bins_task<BPL, FULL, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T, H,
+                                 nullptr, (int)t, n_sel, stride);
     } else {
       unsigned next = 0;
-      bins_task<BPL, FULL, true, GC_ZSUM>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead,
-                                          T, H, &next, (int)t, n_sel, stride);
+      bins_task<BPL, FULL, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T, H,
+                                 &next, (int)t, n_sel, stride);
       if (threadIdx.x == 0) task_s = next;
       __syncthreads();
       ahead.t = task_s;
@@ -1923,13 +1478,13 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_io(FusedArgs A, PipeDev
 template <int BPL, bool FULL>
 __global__ void __launch_bounds__(256, kFusedOcc) k_bins_fused(FusedArgs A) {
   extern __shared__ double lds[];
-  bins_prologue<BPL>(A, lds);
+  bins_prologue(A, lds);
   const int RL = A.B * NF_BASE + REC_EXTRA;
   int64_t n_sel, stride;
   selection_of(A, &n_sel, &stride);
-  bins_task<BPL, FULL, false, GC_ZSUM>(A, blockIdx.y, blockIdx.x, lds,
-                                A.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * RL, nullptr, nullptr,
-                                nullptr, 0u, 1, nullptr, -1, n_sel, stride);
+  bins_task<BPL, FULL, false>(A, blockIdx.y, blockIdx.x, lds,
+                              A.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * RL, nullptr, nullptr,
+                              nullptr, 0u, 1, nullptr, -1, n_sel, stride);
 }
 
 // ================================================================ finalize (a6 + certs)
@@ -1992,18 +1547,12 @@ __global__ void __launch_bounds__(kFinWG) k_bins_finalize(int B, int NF, int64_t
 // per-bin projection delta and mass-epsilon ratio go to aux (H, B, 2) and k_evidence reduces them
 // (finalize_cert), in k_bins_finalize's wave_sum order.
 constexpr int kFinBins = 6;
-// chunk records in flight per lane in the split finalize (one L2 round trip per batch)
-#ifndef GC_FIN_KU
-#define GC_FIN_KU 16
-#endif
+constexpr int kFinKU = 16;  // chunk records in flight per lane in the split finalize (one L2 round trip per batch)
 constexpr int kFinSplitWG = 128;
 // up to this many chunk records per hypothesis (H = 256: 18, C5's 1024: 17) the evidence workgroup of
 // each hypothesis sums its own records (one more L2 round trip per 8 chunks at its start) in place of
 // this kernel's launch; more (H = 32: 80) keep the split kernel, which spreads them over 8 CUs
-#ifndef GC_FOLD_CHUNKS
-#define GC_FOLD_CHUNKS 32
-#endif
-constexpr int64_t kFoldChunks = GC_FOLD_CHUNKS;
+constexpr int64_t kFoldChunks = 32;
 static_assert(kFinBins * NF_BASE + REC_EXTRA <= kFinSplitWG, "one lane per record entry");
 __global__ void __launch_bounds__(kFinSplitWG) k_bins_finalize_split(int B, int NF, int64_t chunks,
                                                                      const double* __restrict__ partials,
@@ -2027,7 +1576,7 @@ __global__ void __launch_bounds__(kFinSplitWG) k_bins_finalize_split(int B, int 
   const int t = threadIdx.x;
   if (t < ne) {
     const int e = e0 + t;
-    constexpr int KU = GC_FIN_KU;
+    constexpr int KU = kFinKU;
     double v = 0.0;
     for (int64_t c = 0; c < chunks; c += KU) {
       double x[KU];
@@ -2296,7 +1845,7 @@ int32_t gc_scan_bin_moment_match(gc_ctx* ctx, int32_t H, int64_t n, int32_t B, c
   const size_t sh = sizeof(double) * std::max<size_t>((size_t)4 * 16 * NT * kMomFS, (size_t)4 * B * NF);
   const bool pair = B >= 32 && ((uintptr_t)d_resp & 15) == 0;
 #define GC_MOM_L(BP, CV, LM, PR)                                                                                 \
-  hipLaunchKernelGGL((k_moment_partials<BP, CV, LM, 1, PR>), grid, dim3(256), sh, ctx->stream, n, B, groups,    \
+  hipLaunchKernelGGL((k_moment_partials<BP, CV, LM, PR>), grid, dim3(256), sh, ctx->stream, n, B, groups,    \
                      d_points, d_covs, d_w, d_resp, d_lambda, o[0], o[1], o[2], (double*)scr)
 #define GC_MOM(BP, CV)                                                                                          \
   do {                                                                                                          \
@@ -2363,6 +1912,31 @@ int32_t gc_scan_bins_fused(gc_ctx* ctx, int32_t H, int64_t n_in, int64_t n_cap, 
 }  // extern "C"
 
 namespace gc {
+// The task tiers of scan_bins_pipeline: long chunks for the bulk, then short ones, then tiny ones.
+// >= 2 long tasks per puller: with the late ticket and the tiny tier the tail no longer needs a third,
+// and fewer, longer tasks amortise each task's set-up and record epilogue: H = 32 4 -> 8 iterations,
+// 92 -> 62 chunks, 0.2892 -> 0.2800 ms/scan (3 tasks: 0.2892, 1: 0.2848; profiles/r04/ab_bins_tail.txt);
+// H >= 64 keep 16
+constexpr int kBinsMinTasks = 2;
+// short tasks of half a long one, at least 2 iterations: H = 256 8-iteration short tasks (interleaved
+// A/B on one box, 1.2499/1.2463 ms/scan with 4 -> 1.2377/1.2391 with 8); H = 32 (4-iteration long
+// tasks) 2, which stays best there (0.3013/0.3004/0.3003 ms against 0.305-0.313 for 8-iteration long
+// tasks with 2- or 4-iteration short ones and for 4-iteration tasks only; tools/ab32.sh)
+constexpr int kShortDiv = 2;
+// a third tier of tiny tasks (a quarter of a short one) at the very end, about one per puller: with
+// the next ticket taken before each task's epilogue (k_bins_io) the pullers' end spread fell from
+// 57 to ~24 us at H = 256 (GC_BINS_TIMING traces); interleaved A/B against the two tiers and the
+// ticket taken at the task start, 1.1999 -> 1.1950 ms at H = 256, 0.2930 -> 0.2903 at H = 32
+// (profiles/r04/ab_bins_tail.txt; 2 tiny tasks per puller, or an eighth or a half of a short task,
+// no better)
+constexpr int kTinyDiv = 4, kTinyPerPuller = 1;
+// the short tier's work: one long task per puller when every puller has at least 4 long tasks (H = 256),
+// three quarters of one with fewer 32-iteration tasks (H = 128: 0.6497 -> 0.6459 ms/scan), half of one when
+// the long tasks are shorter (H = 32's 8 iterations, H = 64's 16): with few long tasks per puller the
+// epilogues of the many short tasks cost more than the finer tail gains (H = 32 0.2586 -> 0.2548 ms/scan;
+// H = 256 1.1624 against 1.1656 with half, 1.1648 with three quarters; profiles/r05/ab_bins_short_share.txt)
+constexpr double kShortShare = 0.5, kShortShare32 = 0.75;
+
 // The batched pipeline's a1 -> a6 bins for its Hl local hypotheses, with the IMU/odom branch's
 // workgroups in the same launch when io (k_bins_io), then the chunk-order finalize.
 int32_t scan_bins_pipeline(gc_ctx* ctx, const PipeDev& P, const ScanArgs& S, const double* d_odom, bool io,
@@ -2385,56 +1959,16 @@ int32_t scan_bins_pipeline(gc_ctx* ctx, const PipeDev& P, const ScanArgs& S, con
   // same for every shard size)
   const int64_t U = (P.n_cap + 255) / 256;  // 256-point units per hypothesis
   const int Hg = P.geom_H > 0 ? P.geom_H : H;
-  // >= 2 long tasks per puller: with the late ticket and the tiny tier (below) the tail no longer
-  // needs a third, and fewer, longer tasks amortise each task's set-up and record epilogue: H = 32
-  // 4 -> 8 iterations, 92 -> 62 chunks, 0.2892 -> 0.2800 ms/scan (3 tasks: 0.2892, 1: 0.2848;
-  // profiles/r04/ab_bins_tail.txt); H >= 64 keep 16
-#ifndef GC_BINS_MIN_TASKS
-#define GC_BINS_MIN_TASKS 2
-#endif
-  constexpr int kBinsMinTasks = GC_BINS_MIN_TASKS;
   // at most 32 iterations (8192 points) per long task: H = 256 1.1935 -> 1.1803 ms, H = 128 0.6706 ->
   // 0.6658 against 16; 64: 1.1872 (profiles/r04/ab_bins_tail.txt)
   int iters = 32;
   while (iters > 2 && (int64_t)Hg * U < kBinsMinTasks * (int64_t)pullers * iters) iters >>= 1;
-#ifndef GC_BINS_SHORT_DIV
-#define GC_BINS_SHORT_DIV 2
-#endif
-  constexpr int kShortDiv = GC_BINS_SHORT_DIV;
-#ifndef GC_BINS_TINY_DIV
-#define GC_BINS_TINY_DIV 4
-#endif
-#ifndef GC_BINS_TINY_PER_PULLER
-#define GC_BINS_TINY_PER_PULLER 1
-#endif
-  constexpr int kTinyDiv = GC_BINS_TINY_DIV, kTinyPerPuller = GC_BINS_TINY_PER_PULLER;
-  // short tasks of half a long one, at least 2 iterations: H = 256 8-iteration short tasks (interleaved
-  // A/B on one box, 1.2499/1.2463 ms/scan with 4 -> 1.2377/1.2391 with 8); H = 32 (4-iteration long
-  // tasks) 2, which stays best there (0.3013/0.3004/0.3003 ms against 0.305-0.313 for 8-iteration long
-  // tasks with 2- or 4-iteration short ones and for 4-iteration tasks only; tools/ab32.sh)
   const int kItersShort = std::max(2, iters / kShortDiv);
-  // a third tier of tiny tasks (a quarter of a short one) at the very end, about one per puller: with
-  // the next ticket taken before each task's epilogue (k_bins_io) the pullers' end spread fell from
-  // 57 to ~24 us at H = 256 (GC_BINS_TIMING traces); interleaved A/B against the two tiers and the
-  // ticket taken at the task start, 1.1999 -> 1.1950 ms at H = 256, 0.2930 -> 0.2903 at H = 32
-  // (profiles/r04/ab_bins_tail.txt; 2 tiny tasks per puller, or an eighth or a half of a short task,
-  // no better)
   const int kItersTiny = std::max(1, kItersShort / kTinyDiv);
   int64_t Ut = ((int64_t)pullers * kItersTiny * kTinyPerPuller + Hg - 1) / Hg;
   Ut = std::min<int64_t>((Ut + kItersTiny - 1) / kItersTiny * kItersTiny, U);
-  // the short tier's work: one long task per puller when every puller has at least 4 long tasks (H = 256),
-  // three quarters of one with fewer 32-iteration tasks (H = 128: 0.6497 -> 0.6459 ms/scan), half of one when
-  // the long tasks are shorter (H = 32's 8 iterations, H = 64's 16): with few long tasks per puller the
-  // epilogues of the many short tasks cost more than the finer tail gains (H = 32 0.2586 -> 0.2548 ms/scan;
-  // H = 256 1.1624 against 1.1656 with half, 1.1648 with three quarters; profiles/r05/ab_bins_short_share.txt)
-#ifndef GC_BINS_SHORT_SHARE
-#define GC_BINS_SHORT_SHARE 0.5
-#endif
-#ifndef GC_BINS_SHORT_SHARE_32
-#define GC_BINS_SHORT_SHARE_32 0.75
-#endif
   const bool many_long = (int64_t)Hg * U >= 4 * (int64_t)pullers * iters;
-  const double short_share = many_long ? 1.0 : (iters >= 32 ? GC_BINS_SHORT_SHARE_32 : GC_BINS_SHORT_SHARE);
+  const double short_share = many_long ? 1.0 : (iters >= 32 ? kShortShare32 : kShortShare);
   int64_t Us = std::max<int64_t>(iters, (int64_t)(short_share * (double)pullers * iters + Hg - 1) / Hg);
   Us = std::min(Us, U - Ut);
   const int64_t k1 = (U - Ut - Us) / iters;  // long chunks; the short and tiny tiers take the rest

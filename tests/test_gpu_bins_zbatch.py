@@ -1,9 +1,11 @@
-"""The fused bins kernels with the softmax normaliser's batched 16-lane sum (gc_points.hip group16_sum2 /
-group16_sum4, GC_ZSUM = 4 / 3; the per-step butterfly is GC_ZSUM = 0): every instantiation of the grid
-form against the oracle chain, and bit identity with what the library computed before the batched form
-existed (tests/golden/bins_fused_parent.npz, pipeline_small_parent.npz; recorded by
+"""The fused bins kernels with the softmax normaliser's batched 16-lane sum (gc_points.hip group16_sum2;
+B = 16 keeps the per-step butterfly, group16_sum): every instantiation of the grid form against the oracle
+chain, and bit identity with what the library computed before the batched form existed
+(tests/golden/bins_fused_parent.npz, pipeline_small_parent.npz; recorded by
 tests/golden/make_bins_zbatch_parent.py). The batched sum adds the same partials in the same
-association, so whichever form a build selects, the outputs are the recorded bits.
+association, so the outputs are the recorded bits. The build switch that selected between these forms, the
+batch of four and the swizzle sums was removed; the last commit whose tree holds them is dd48cdd, their
+measurements are in profiles/r07/ab_bins_zbatch.txt and profiles/r06/ab_zsum_swizzle.txt.
 
 The late-ticket instantiation of k_bins_io (H = 256) is too large for a test of seconds: its outputs are
 compared byte for byte with bench.py --dump-outputs (profiles/r07/ab_bins_zbatch.txt)."""

@@ -1,6 +1,9 @@
 """Dev probe (GPU box): per-workgroup timing of the last k_bins_io launch after a short bench run with
-a GC_BINS_TIMING build (tools/variant.sh btime gc_points -DGC_BINS_TIMING).
-Usage: python3 tools/probe/bins_trace.py <libgcslam.so> <H>"""
+a library built with -DGC_BINS_TIMING:
+    mkdir -p fl-slam_amd/build_var/btime
+    make -C fl-slam_amd BUILD=build_bt OUT=build_var/btime/libgcslam.so \
+        CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -I../include -DGC_BINS_TIMING"
+Usage: python3 tools/probe/bins_trace.py fl-slam_amd/build_var/btime/libgcslam.so <H>"""
 import ctypes as C
 import os
 import sys
