@@ -14,6 +14,7 @@
 // Sinkhorn couples all rows through the column sums, so it runs in one 1024-thread workgroup with
 // fixed-order block reductions (deterministic), the N x K kernel matrix streamed from L2.
 #include <hip/hip_runtime.h>
+#include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
 #include "gc_mapslot.h"
@@ -246,30 +247,6 @@ __global__ void __launch_bounds__(256) k_assoc_rows(int64_t N, int L, const doub
   }
 }
 
-// fixed-order block reduction of NV values over kSinkT threads; result on every thread
-template <int NV>
-GC_DEV void block_sum_n(double (&v)[NV], double* red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    v[q] = x;
-  }
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int q = 0; q < NV; ++q) red[wv * NV + q] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double s = 0.0;
-    for (int w = 0; w < kSinkT / 64; ++w) s += red[w * NV + q];
-    v[q] = s;
-  }
-  __syncthreads();
-}
-
 // unbalanced Sinkhorn, fixed iterations (_sinkhorn_unbalanced_fixed_k_jax) + outputs and certs
 __global__ void __launch_bounds__(kSinkT) k_sinkhorn(int64_t N, const uint8_t* __restrict__ valid,
                                                      const double* __restrict__ wts, OTCfg c,
@@ -284,7 +261,7 @@ __global__ void __launch_bounds__(kSinkT) k_sinkhorn(int64_t N, const uint8_t* _
   double s1[1] = {0.0};
   for (int64_t i = threadIdx.x; i < N; i += kSinkT)
     s1[0] += valid[i] ? (c.wprop ? wts[i] : 1.0) : 0.0;
-  block_sum_n<1>(s1, red);
+  block_sum<1, kSinkT / 64>(s1, red);
   const double sum_a = fmax(s1[0], c.eps_mass);
   if ((int)threadIdx.x < K) vv[threadIdx.x] = 1.0;
   __syncthreads();
@@ -300,8 +277,10 @@ __global__ void __launch_bounds__(kSinkT) k_sinkhorn(int64_t N, const uint8_t* _
       u[i] = ui;
       for (int q = 0; q < K; ++q) cs[q] += kr[q] * ui;
     }
-    block_sum_n<kMaxK>(cs, red);
-    if ((int)threadIdx.x < K) vv[threadIdx.x] = pow(bk / (cs[threadIdx.x] + 1e-12), vb);
+    // only thread q needs column q's total: the halves of block_sum, the barrier below closing red and vv
+    block_sum_stage<kMaxK>(cs, red);
+    if ((int)threadIdx.x < K)
+      vv[threadIdx.x] = pow(bk / (block_sum_total<kMaxK, kSinkT / 64>(red, threadIdx.x) + 1e-12), vb);
     __syncthreads();
   }
   // π = u K v; responsibilities, row masses and the cert sums
@@ -328,7 +307,7 @@ __global__ void __launch_bounds__(kSinkT) k_sinkhorn(int64_t N, const uint8_t* _
     acc[kMaxK + 5] += a > c.eps_mass ? 1.0 : 0.0;
     acc[kMaxK + 6] += vi ? 1.0 : 0.0;
   }
-  block_sum_n<kMaxK + 7>(acc, red);
+  block_sum<kMaxK + 7, kSinkT / 64>(acc, red);
   if (threadIdx.x == 0) {
     double db = 0.0;
     for (int q = 0; q < K; ++q) db += (acc[q] - bk) * (acc[q] - bk);
@@ -381,20 +360,21 @@ int32_t gc_extract_map_view(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_
     GC_CHECK_ARG(ctx, h_dense_tiles[t] < 0 || (h_dense_tiles[t] + 1) * m_tile <= map->m_slots, "dense tile outside map");
   const int64_t n = (int64_t)T * m_tile;
   GC_CHECK_ARG(ctx, n < (int64_t)INT32_MAX, "view too large");
-  const size_t temp = gc::sort_temp_bytes(T, m_tile, true);
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t bk = al(sizeof(double) * n), bv = al(sizeof(int32_t) * n), bo = al(sizeof(int) * (T + 1)),
-               bd = al(sizeof(int64_t) * T);
-  void* scr;
-  if (int rc = gc::scratch(ctx, 2 * bk + 2 * bv + bo + bd + temp, &scr)) return rc;
-  char* p = (char*)scr;
-  double* keys_in = (double*)p; p += bk;
-  double* keys = (double*)p; p += bk;
-  int32_t* vals_in = (int32_t*)p; p += bv;
-  int32_t* vals = (int32_t*)p; p += bv;
-  int* offs = (int*)p; p += bo;
-  int64_t* dense = (int64_t*)p; p += bd;
-  void* tmp = p;
+  double *keys_in, *keys;
+  int32_t *vals_in, *vals;
+  int* offs;
+  int64_t* dense;
+  void* tmp;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        keys_in = c.take<double>(n);
+        keys = c.take<double>(n);
+        vals_in = c.take<int32_t>(n);
+        vals = c.take<int32_t>(n);
+        offs = c.take<int>(T + 1);
+        dense = c.take<int64_t>(T);
+        tmp = c.take<char>(gc::sort_temp_bytes(T, m_tile, true));
+      }))
+    return rc;
   GC_HIP(ctx, hipMemcpyAsync(dense, h_dense_tiles, sizeof(int64_t) * T, hipMemcpyHostToDevice, ctx->stream));
   GC_HIP(ctx, hipMemcpyAsync(view->tile_ids, h_tile_ids, sizeof(int64_t) * T, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_view_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *map, m_tile,
@@ -450,15 +430,15 @@ int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, cons
   const int64_t pool = (2 * c.r_z + 1) * (int64_t)n_xy * view->m_tile_view;
   GC_CHECK_ARG(ctx, V >= 1 && pool >= c.K && pool < (int64_t)INT32_MAX, "bad view / pool smaller than k_assoc");
   for (int q = 0; q < GC_OT_CERT_LEN; ++q) h_cert_out[q] = 0.0;
-  void* scr;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t bkm = al(sizeof(double) * N * c.K), bu = al(sizeof(double) * N), bc = al(64 * sizeof(double));
-  if (int rc = gc::scratch(ctx, bkm + bu + bc + 256, &scr)) return rc;
-  char* p = (char*)scr;
-  double* kmat = (double*)p; p += bkm;
-  double* u = (double*)p; p += bu;
-  double* cert = (double*)p; p += bc;
-  unsigned long long* cnt = (unsigned long long*)p;
+  double *kmat, *u, *cert;
+  unsigned long long* cnt;  // the valid counts of the rows and of the view
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& s) {
+        kmat = s.take<double>((size_t)N * c.K);
+        u = s.take<double>(N);
+        cert = s.take<double>(64);
+        cnt = s.take<unsigned long long>(2);
+      }))
+    return rc;
   // the empty-input no-op (primitive_association.py:271-287) needs both valid counts
   GC_HIP(ctx, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(k_count_u8, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, N, d_valid, cnt);

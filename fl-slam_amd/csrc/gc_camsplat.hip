@@ -20,8 +20,8 @@
 //                into a list of its own; the four lists one after the other are the candidates in
 //                ascending point index, whatever the scheduling. Route A: the median of z and of
 //                |z - median| by an LDS bitonic sort, the mean and the population variance by
-//                fixed-order sums. Route B: a bitonic sort by (squared distance to the ray, candidate
-//                position), the first k_use of it one per thread, the weighted centroid and scatter by
+//                fixed-order sums (block_sum, gc_blocksum.h). Route B: a bitonic sort by (squared
+//                distance to the ray, candidate position), the first k_use of it one per thread, the weighted centroid and scatter by
 //                fixed-order sums, eigh3, the ray-plane intersection and the reliabilities.
 //  k_cs_finish   one lane per row: the PoE fusion with its fall-backs, the backprojection and its
 //                closed-form covariance, the base-frame transform, Λ = inv3(Σ + eps_lift I), θ = Λ μ, the
@@ -30,6 +30,7 @@
 //                given positions and covariances.
 #include <hip/hip_runtime.h>
 #include <string>
+#include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
 
@@ -86,27 +87,6 @@ __global__ void __launch_bounds__(kCsT) k_cs_project(int64_t N, const double* __
   }
   const unsigned long long b = __ballot(front);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_front, __popcll(b));  // an integer count: any order
-}
-
-// the totals of NV per-thread values for every thread: an xor butterfly in each wave, then the waves'
-// partials added in wave order. red: kCsWaves * NV doubles.
-template <int NV>
-GC_DEV void cs_block_sum(double* v, double* red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    if (lane == 0) red[wv * NV + q] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double x = red[q];
-    for (int u = 1; u < kCsWaves; ++u) x += red[u * NV + q];
-    v[q] = x;
-  }
-  __syncthreads();
 }
 
 // ascending bitonic sort of P (a power of two, <= kCsMaxNear) (key, val) pairs in LDS, val breaking ties
@@ -226,14 +206,14 @@ __global__ void __launch_bounds__(kCsT) k_cs_query(int64_t N, const double2* __r
   __syncthreads();
   double s1[1] = {0.0};
   for (int j = t; j < n; j += kCsT) s1[0] += cz[j];
-  cs_block_sum<1>(s1, red);
+  block_sum<1, kCsWaves>(s1, red);
   const double z_mean = s1[0] / (double)n;
   s1[0] = 0.0;
   for (int j = t; j < n; j += kCsT) {
     const double d = cz[j] - z_mean;
     s1[0] += d * d;
   }
-  cs_block_sum<1>(s1, red);
+  block_sum<1, kCsWaves>(s1, red);
   const double var_spread = n >= 2 ? s1[0] / (double)n : 0.0;  // np.var: the population variance
   const double sigma_A = 1.4826 * mad, sigma_A_sq = sigma_A * sigma_A;
   double sig_a = cfg.base_sigma * cfg.base_sigma + fmax(sigma_A_sq, var_spread);
@@ -281,14 +261,14 @@ __global__ void __launch_bounds__(kCsT) k_cs_query(int64_t N, const double2* __r
     w = pw ? pw[i] : 1.0;
   }
   double a4[4] = {w, w * p[0], w * p[1], w * p[2]};
-  cs_block_sum<4>(a4, red);
+  block_sum<4, kCsWaves>(a4, red);
   const double sw = a4[0], w_sum = sw + 1e-300;
   const double cen[3] = {a4[1] / sw, a4[2] / sw, a4[3] / sw};
   const double c0 = p[0] - cen[0], c1 = p[1] - cen[1], c2 = p[2] - cen[2];
   double a6[6] = {w * c0 * c0, w * c0 * c1, w * c0 * c2, w * c1 * c1, w * c1 * c2, w * c2 * c2};
   if (!(t < k_use))
     for (int q = 0; q < 6; ++q) a6[q] = 0.0;  // cen may be NaN for an all-zero weight sum
-  cs_block_sum<6>(a6, red);
+  block_sum<6, kCsWaves>(a6, red);
   const double sxx = a6[0] / w_sum, sxy = a6[1] / w_sum, sxz = a6[2] / w_sum, syy = a6[3] / w_sum,
                syz = a6[4] / w_sum, szz = a6[5] / w_sum;
   const double S[9] = {sxx + 1e-12, sxy, sxz, sxy, syy + 1e-12, syz, sxz, syz, szz + 1e-12};
@@ -306,7 +286,7 @@ __global__ void __launch_bounds__(kCsT) k_cs_query(int64_t N, const double2* __r
   if (nrm[2] < 0.0) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }
   const double res = c0 * nrm[0] + c1 * nrm[1] + c2 * nrm[2];
   s1[0] = t < k_use ? w * (res * res) : 0.0;
-  cs_block_sum<1>(s1, red);
+  block_sum<1, kCsWaves>(s1, red);
   const double sigma_perp_sq = fmax(s1[0] / sw, 0.0);
   if (t != 0) return;
   const double ndr = nrm[0] * ray[0] + nrm[1] * ray[1] + nrm[2] * ray[2];
@@ -502,16 +482,12 @@ struct CsScratch {
 };
 
 int cs_scratch(gc_ctx* ctx, int64_t N, CsScratch* s) {
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t npt = (size_t)(N > 0 ? N : 1);
-  const size_t buv = al(sizeof(double2) * npt), bpc = al(sizeof(double) * 3 * npt), bw = al(2 * sizeof(int32_t));
-  void* scr;
-  if (int rc = gc::scratch(ctx, buv + bpc + bw, &scr)) return rc;
-  char* p = (char*)scr;
-  s->uv = (double2*)p; p += buv;
-  s->pcam = (double*)p; p += bpc;
-  s->words = (int32_t*)p;
-  return GC_OK;
+  return gc::carve_scratch(ctx, [&](gc::Carver& c) {
+    s->uv = c.take<double2>(npt);
+    s->pcam = c.take<double>(3 * npt);
+    s->words = c.take<int32_t>(2);
+  });
 }
 
 // project and query: the evidence rows (M, GC_CAM_EV) and the in-radius counts (M)

@@ -83,6 +83,35 @@ int join_side(gc_ctx* ctx);
 // device scratch of at least `bytes` (synchronises the stream before growing)
 int scratch(gc_ctx* ctx, size_t bytes, void** out);
 
+constexpr size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// Carves one block of device scratch into typed arrays, each on a 256-byte boundary of the block. A
+// layout is written once, as code that asks a Carver for its arrays in order, and run twice: without a
+// base it only adds up `bytes` (the pointers it hands out are null), with the base it hands out the
+// arrays. The byte total and the pointers therefore cannot disagree.
+struct Carver {
+  char* base = nullptr;
+  size_t bytes = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + bytes) : nullptr;
+    bytes += align256(sizeof(T) * count);
+    return p;
+  }
+};
+
+// the context's scratch (gc::scratch) carved by `layout`, a callable taking Carver&
+template <typename Layout>
+int carve_scratch(gc_ctx* ctx, Layout&& layout) {
+  Carver size;
+  layout(size);
+  void* scr;
+  if (int rc = scratch(ctx, size.bytes, &scr)) return rc;
+  Carver c{(char*)scr};
+  layout(c);
+  return GC_OK;
+}
+
 // a run hash (gc_runs.h RunTable) of at least 2^kRunLoadShift x rows entries, every entry empty on return
 // (stream-ordered: a fill is enqueued on st when the table is new, grown or dirty)
 int run_table(gc_ctx* ctx, hipStream_t st, RunTableBuf* T, int64_t rows);

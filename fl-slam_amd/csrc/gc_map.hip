@@ -481,11 +481,25 @@ hipError_t launch_fuse_colors(const gc_primitive_map& map, double eps_mass, hipS
   return hipGetLastError();
 }
 // scratch of fuse_launch for K rows: the sorted slot, row order, run length and owner's entry of every
-// position and the apply launch's per-workgroup distinct-slot counts
+// position and the apply launch's per-workgroup distinct-slot counts (the run hash and its links are the
+// context's)
+struct FuseScratch {
+  uint32_t *sslot, *order, *run_len, *rank, *cnt;
+};
+static FuseScratch fuse_layout(Carver& c, int64_t K) {
+  const size_t wg = (size_t)(kFuseBlk < kApplyWG ? kFuseBlk : kApplyWG);  // the apply grid is at most ⌈K / wg⌉
+  FuseScratch s;
+  s.sslot = c.take<uint32_t>(K);
+  s.order = c.take<uint32_t>(K);
+  s.run_len = c.take<uint32_t>(K);
+  s.rank = c.take<uint32_t>(K);
+  s.cnt = c.take<uint32_t>(((size_t)K + wg - 1) / wg);
+  return s;
+}
 size_t fuse_scratch_bytes(int64_t K) {
-  const size_t kv = ((size_t)K * sizeof(uint32_t) + 255) / 256 * 256;
-  const size_t wg = (size_t)(kFuseBlk < kApplyWG ? kFuseBlk : kApplyWG);
-  return 4 * kv + ((size_t)K + wg - 1) / wg * sizeof(uint32_t) + 256;
+  Carver c;
+  fuse_layout(c, K);
+  return c.bytes;
 }
 
 // The launches of gc_primitive_map_fuse on validated arguments with K >= 1 rows (no host wait once the
@@ -520,20 +534,14 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
   }
   A.timestamp = timestamp;
   A.scan_seq = scan_seq;
-  // scratch: the sorted slot, row order, run length and owner's entry of every position, the apply
-  // launch's per-workgroup distinct-slot counts (the run hash and its links are the context's)
-  const size_t kv = ((size_t)K * sizeof(uint32_t) + 255) / 256 * 256;
   // the packed record's apply with the sort block's rows staged in LDS (k_fuse_apply_blk: one workgroup per
   // sort block); other layouts gather the rows from HBM by 128-position workgroups (k_fuse_apply)
   const bool staged = A.rec32;
   const unsigned nblk = (unsigned)((K + kFuseBlk - 1) / kFuseBlk);
   const unsigned grid = staged ? nblk : (unsigned)((K + kApplyWG - 1) / kApplyWG);
-  char* base = (char*)scr;
-  uint32_t* sslot = (uint32_t*)base;
-  uint32_t* order = (uint32_t*)(base + kv);
-  uint32_t* run_len = (uint32_t*)(base + 2 * kv);
-  uint32_t* rank = (uint32_t*)(base + 3 * kv);
-  uint32_t* cnt = (uint32_t*)(base + 4 * kv);
+  Carver carve{(char*)scr};
+  const FuseScratch s = fuse_layout(carve, K);
+  uint32_t *sslot = s.sslot, *order = s.order, *run_len = s.run_len, *rank = s.rank, *cnt = s.cnt;
   if (int rc = gc::run_table(ctx, ctx->stream, &ctx->runs, K)) return rc;
   const RunTable T{ctx->runs.entries(), ctx->runs.succ(), ctx->runs.bits};
   // from here a failed launch may leave entries set: the next call empties them

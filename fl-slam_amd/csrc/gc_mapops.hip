@@ -15,6 +15,7 @@
 // inherently sequential and runs on one lane over the sorted candidates, stopping at the first
 // distance >= threshold.
 #include <hip/hip_runtime.h>
+#include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
 #include "gc_mapslot.h"
@@ -32,14 +33,16 @@ struct Tile {
   int64_t s0, n;
 };
 
-// Fixed-order block sum of NV per-thread values into part[blockIdx.x * NV + v].
+// Fixed-order block sum of NV per-thread values into part[blockIdx.x * NV + v]. The wave step is the
+// butterfly of gc_blocksum.h; the four waves are added pairwise, (w0 + w1) + (w2 + w3), not in
+// block_sum's sequential wave order: the maintenance operators have always summed so, and another
+// association changes their bits.
 template <int NV>
 GC_DEV void block_partials(double (&v)[NV], double* part) {
   __shared__ double red[NV][4];
 #pragma unroll
   for (int q = 0; q < NV; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    const double x = group_sum_xor<64>(v[q]);
     if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = x;
   }
   __syncthreads();
@@ -363,13 +366,29 @@ int download(gc_ctx* ctx, void* h, const void* d, size_t bytes) {
   return GC_OK;
 }
 
+// scratch of insert_launch on a tile of n_slots: the reduction partials with the two results behind them
+// (part + kPartBlocks), the retention keys and slot numbers before and after the sort, and the sort's own
+struct InsertScratch {
+  double *part, *keys_in, *keys;
+  int32_t *vals_in, *vals;
+  void* tmp;
+};
+InsertScratch insert_layout(Carver& c, int64_t n_slots) {
+  InsertScratch s;
+  s.part = c.take<double>(kPartBlocks + 16);
+  s.keys_in = c.take<double>(n_slots);
+  s.keys = c.take<double>(n_slots);
+  s.vals_in = c.take<int32_t>(n_slots);
+  s.vals = c.take<int32_t>(n_slots);
+  s.tmp = c.take<char>(gc::sort_temp_bytes(1, n_slots, true));
+  return s;
+}
+
 }  // namespace
-// scratch of insert_launch on a tile of n_slots: the reduction partials, the retention keys and slot
-// numbers before and after the sort, and the sort's own
 size_t insert_scratch_bytes(int64_t n_slots) {
-  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
-  const size_t vb = ((size_t)n_slots * sizeof(int32_t) + 255) / 256 * 256;
-  return sizeof(double) * (kPartBlocks + 16) + 2 * kb + 2 * vb + gc::sort_temp_bytes(1, n_slots, true);
+  Carver c;
+  insert_layout(c, n_slots);
+  return c.bytes;
 }
 
 // The launches of gc_primitive_map_insert_masked on validated arguments (no host wait): scr holds
@@ -379,30 +398,22 @@ int insert_launch(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64
                   const gc_insert_batch* batch, double timestamp, int64_t scan_seq, double recency_decay_lambda,
                   int64_t next_global_id, const int64_t* d_id_offset, int32_t* d_target_slots_out,
                   int64_t* d_new_ids_out, void* scr, double* d_out2) {
-  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
-  const size_t vb = ((size_t)n_slots * sizeof(int32_t) + 255) / 256 * 256;
-  const size_t head = sizeof(double) * (kPartBlocks + 16);
-  double* part = (double*)scr;
-  char* base = (char*)scr + head;
-  double* keys_in = (double*)base;
-  double* keys = (double*)(base + kb);
-  int32_t* vals_in = (int32_t*)(base + 2 * kb);
-  int32_t* vals = (int32_t*)(base + 2 * kb + vb);
-  void* tmp = base + 2 * kb + 2 * vb;
+  Carver carve{(char*)scr};
+  const InsertScratch s = insert_layout(carve, n_slots);
   const Tile T{*map, slot0, n_slots};
   hipLaunchKernelGGL(k_insert_keys, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, scan_seq,
-                     recency_decay_lambda, keys_in, vals_in);
+                     recency_decay_lambda, s.keys_in, s.vals_in);
   GC_LAUNCH_CHECK(ctx);
-  if (gc::radix_sort_pairs(ctx->stream, keys_in, keys, (const uint32_t*)vals_in, (uint32_t*)vals, 1, n_slots, false,
-                           tmp) != hipSuccess) {
+  if (gc::radix_sort_pairs(ctx->stream, s.keys_in, s.keys, (const uint32_t*)s.vals_in, (uint32_t*)s.vals, 1, n_slots,
+                           false, s.tmp) != hipSuccess) {
     gc::set_error(ctx, "radix sort failed");
     return GC_ERR_RUNTIME;
   }
-  hipLaunchKernelGGL(k_insert_apply, dim3(1), dim3(256), 0, ctx->stream, T, *batch, (const int32_t*)vals, timestamp,
+  hipLaunchKernelGGL(k_insert_apply, dim3(1), dim3(256), 0, ctx->stream, T, *batch, (const int32_t*)s.vals, timestamp,
                      scan_seq, next_global_id, d_id_offset, d_target_slots_out, d_new_ids_out, d_out2 + 1);
   GC_LAUNCH_CHECK(ctx);
-  if (int rc = reduce_into<1>(ctx, n_slots, part, d_out2, [&](unsigned nb) {
-        hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, part);
+  if (int rc = reduce_into<1>(ctx, n_slots, s.part, d_out2, [&](unsigned nb) {
+        hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, s.part);
       }))
     return rc;
   return GC_OK;
@@ -429,10 +440,12 @@ int32_t gc_primitive_map_recency_inflate(gc_ctx* ctx, const gc_primitive_map* ma
   if (int rc = check_tile(ctx, map, slot0, n_slots, true)) return rc;
   if (h_stats3) h_stats3[0] = h_stats3[1] = h_stats3[2] = 0.0;
   if (n_slots == 0) return GC_OK;
-  void* scr;
-  if (int rc = gc::scratch(ctx, sizeof(double) * (3 * kPartBlocks + 8), &scr)) return rc;
-  double* part = (double*)scr;
-  double* out = part + 3 * kPartBlocks;
+  double *part, *out;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        part = c.take<double>(3 * kPartBlocks);
+        out = c.take<double>(3);
+      }))
+    return rc;
   const Tile T{*map, slot0, n_slots};
   if (int rc = reduce_into<3>(ctx, n_slots, part, out, [&](unsigned nb) {
         hipLaunchKernelGGL(k_recency, dim3(nb), dim3(256), 0, ctx->stream, T, scan_seq, decay_lambda, min_scale,
@@ -462,15 +475,16 @@ int32_t gc_primitive_map_cull(gc_ctx* ctx, const gc_primitive_map* map, int64_t 
   GC_CHECK_ARG(ctx, h_out4 != nullptr, "h_out4 is NULL");
   for (int q = 0; q < 4; ++q) h_out4[q] = 0.0;
   if (n_slots == 0) return GC_OK;
-  const size_t temp = gc::sort_temp_bytes(1, n_slots, false);
-  const size_t kb = ((size_t)n_slots * sizeof(double) + 255) / 256 * 256;
-  void* scr;
-  if (int rc = gc::scratch(ctx, sizeof(double) * (4 * kPartBlocks + 8) + 2 * kb + temp, &scr)) return rc;
-  double* part = (double*)scr;
-  double* out = part + 4 * kPartBlocks;
-  double* keys_in = (double*)((char*)scr + sizeof(double) * (4 * kPartBlocks + 8));
-  double* keys = (double*)((char*)keys_in + kb);
-  void* tmp = (char*)keys + kb;
+  double *part, *out, *keys_in, *keys;
+  void* tmp;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        part = c.take<double>(4 * kPartBlocks);
+        out = c.take<double>(4);
+        keys_in = c.take<double>(n_slots);
+        keys = c.take<double>(n_slots);
+        tmp = c.take<char>(gc::sort_temp_bytes(1, n_slots, false));
+      }))
+    return rc;
   const Tile T{*map, slot0, n_slots};
   auto count = [&](double thr, double* h4) -> int {
     if (int rc = reduce_into<4>(ctx, n_slots, part, out, [&](unsigned nb) {
@@ -517,7 +531,8 @@ int32_t gc_primitive_map_insert_masked(gc_ctx* ctx, const gc_primitive_map* map,
                "NULL proposal field");
   void* scr;
   if (int rc = gc::scratch(ctx, gc::insert_scratch_bytes(n_slots), &scr)) return rc;
-  double* out = (double*)scr + kPartBlocks;  // [count_after, n_inserted]
+  gc::Carver carve{(char*)scr};
+  double* out = insert_layout(carve, n_slots).part + kPartBlocks;  // [count_after, n_inserted]
   if (int rc = gc::insert_launch(ctx, map, slot0, n_slots, batch, timestamp, scan_seq, recency_decay_lambda,
                                  next_global_id, nullptr, d_target_slots_out, d_new_ids_out, scr, out))
     return rc;
@@ -538,28 +553,26 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
   h_out2[1] = 0;
   const Tile T{*map, slot0, n_slots};
   const int64_t P = n_slots * (n_slots - 1) / 2;
-  const size_t temp = P > 0 ? gc::sort_temp_bytes(1, P, true) : 0;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t head = sizeof(double) * (kPartBlocks + 16);
-  const size_t b_mu = al(sizeof(double) * 3 * n_slots), b_sig = al(sizeof(double) * 9 * n_slots),
-               b_det = al(sizeof(double) * n_slots), b_k = al(sizeof(double) * P), b_v = al(sizeof(uint32_t) * P),
-               b_used = al(n_slots), b_sel = al(sizeof(int32_t) * (2 * (size_t)(max_pairs > 0 ? max_pairs : 1) + 1));
-  void* scr;
-  if (int rc = gc::scratch(ctx, head + b_mu + b_sig + b_det + 2 * b_k + 2 * b_v + b_used + b_sel + temp, &scr))
+  double *part, *out, *mu, *Sig, *dets, *keys_in, *keys;
+  uint32_t *vals_in, *vals;
+  uint8_t* used;
+  int32_t* sel;  // max_pairs pairs, then their count
+  void* tmp;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        part = c.take<double>(kPartBlocks);
+        out = c.take<double>(1);
+        mu = c.take<double>(3 * (size_t)n_slots);
+        Sig = c.take<double>(9 * (size_t)n_slots);
+        dets = c.take<double>(n_slots);
+        keys_in = c.take<double>(P);
+        keys = c.take<double>(P);
+        vals_in = c.take<uint32_t>(P);
+        vals = c.take<uint32_t>(P);
+        used = c.take<uint8_t>(n_slots);
+        sel = c.take<int32_t>(2 * (size_t)(max_pairs > 0 ? max_pairs : 1) + 1);
+        tmp = c.take<char>(P > 0 ? gc::sort_temp_bytes(1, P, true) : 0);
+      }))
     return rc;
-  double* part = (double*)scr;
-  double* out = part + kPartBlocks;
-  char* p = (char*)scr + head;
-  double* mu = (double*)p; p += b_mu;
-  double* Sig = (double*)p; p += b_sig;
-  double* dets = (double*)p; p += b_det;
-  double* keys_in = (double*)p; p += b_k;
-  double* keys = (double*)p; p += b_k;
-  uint32_t* vals_in = (uint32_t*)p; p += b_v;
-  uint32_t* vals = (uint32_t*)p; p += b_v;
-  uint8_t* used = (uint8_t*)p; p += b_used;
-  int32_t* sel = (int32_t*)p; p += b_sel;
-  void* tmp = p;
   auto count_valid = [&](double* h) -> int {
     if (int rc = reduce_into<1>(ctx, n_slots, part, out, [&](unsigned nb) {
           hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, part);

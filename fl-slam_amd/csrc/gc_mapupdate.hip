@@ -335,8 +335,6 @@ __global__ void k_mu_ids(const int64_t* __restrict__ n_new, int n_active, int64_
   }
 }
 
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace gc
 
@@ -396,39 +394,34 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
   // fuse's and the inserts' own (used one after the other)
   // one flag byte per (block, slot number); the distinct-slot counter sits behind them, 8-B aligned
   const size_t flag_bytes = ((size_t)(n_blocks * m_tile) + 7) / 8 * 8;
-  size_t off = 0;
-  const auto take = [&off](size_t bytes) {
-    const size_t o = off;
-    off += al256(bytes);
-    return o;
-  };
-  const size_t o_slots = take(4 * NK), o_Lam = take(72 * NK), o_th = take(24 * NK), o_et = take(24 * (size_t)L * NK),
-               o_w = take(8 * NK), o_resp = take(8 * NK), o_col = take(24 * NK), o_src = take(4 * NK),
-               o_mass = take(8 * NK), o_flags = take(flag_bytes + 8),
-               o_pet = take(24 * (size_t)L * AK),
-               o_pcol = take(24 * AK), o_psrc = take(4 * AK), o_nnew = take(8 * (size_t)na),
-               o_idoff = take(8 * (size_t)na);
-  const size_t sub = std::max(gc::fuse_scratch_bytes(NK), gc::insert_scratch_bytes(m_tile));
-  const size_t o_sub = take(sub);
-  void* scr;
-  if (int rc = gc::scratch(ctx, off, &scr)) return rc;
-  if (int rc = gc::run_table(ctx, ctx->stream, &ctx->runs, NK)) return rc;
-  const size_t plan_lds = al256((size_t)N * 13 + (size_t)k * 13 + 96 + 4 * kMuWG + 16);
-  GC_HIP(ctx, gc::ensure_dyn_lds((const void*)k_mu_plan, plan_lds));
-  char* base = (char*)scr;
-  int32_t* f_slots = (int32_t*)(base + o_slots);
-  double* f_Lam = (double*)(base + o_Lam);
-  double* f_th = (double*)(base + o_th);
-  double* f_et = (double*)(base + o_et);
-  double* f_w = (double*)(base + o_w);
-  double* f_resp = (double*)(base + o_resp);
-  double* f_col = (double*)(base + o_col);
-  int32_t* f_src = (int32_t*)(base + o_src);
-  double* mass = (double*)(base + o_mass);
-  uint8_t* flags = (uint8_t*)(base + o_flags);
+  int32_t *f_slots, *f_src, *p_src;
+  double *f_Lam, *f_th, *f_et, *f_w, *f_resp, *f_col, *mass, *p_et, *p_col;
+  uint8_t* flags;
+  int64_t *n_new, *id_off;
+  char* sub;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        f_slots = c.take<int32_t>(NK);
+        f_Lam = c.take<double>(9 * (size_t)NK);
+        f_th = c.take<double>(3 * (size_t)NK);
+        f_et = c.take<double>(3 * (size_t)L * NK);
+        f_w = c.take<double>(NK);
+        f_resp = c.take<double>(NK);
+        f_col = c.take<double>(3 * (size_t)NK);
+        f_src = c.take<int32_t>(NK);
+        mass = c.take<double>(NK);
+        flags = c.take<uint8_t>(flag_bytes + 8);
+        p_et = c.take<double>(3 * (size_t)L * AK);
+        p_col = c.take<double>(3 * (size_t)AK);
+        p_src = c.take<int32_t>(AK);
+        n_new = c.take<int64_t>(na);
+        id_off = c.take<int64_t>(na);
+        sub = c.take<char>(std::max(gc::fuse_scratch_bytes(NK), gc::insert_scratch_bytes(m_tile)));
+      }))
+    return rc;
   unsigned long long* n_distinct = (unsigned long long*)(flags + flag_bytes);
-  int64_t* n_new = (int64_t*)(base + o_nnew);
-  int64_t* id_off = (int64_t*)(base + o_idoff);
+  if (int rc = gc::run_table(ctx, ctx->stream, &ctx->runs, NK)) return rc;
+  const size_t plan_lds = gc::align256((size_t)N * 13 + (size_t)k * 13 + 96 + 4 * kMuWG + 16);
+  GC_HIP(ctx, gc::ensure_dyn_lds((const void*)k_mu_plan, plan_lds));
 
   MuArgs A{};
   A.map = *map;
@@ -461,7 +454,7 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
   GC_LAUNCH_CHECK(ctx);
   uint32_t* cnt = nullptr;
   unsigned ncnt = 0;
-  if (int rc = gc::fuse_launch(ctx, &A.map, &F, h_pose6, eps_lift, eps_mass, timestamp, scan_seq, base + o_sub, &cnt,
+  if (int rc = gc::fuse_launch(ctx, &A.map, &F, h_pose6, eps_lift, eps_mass, timestamp, scan_seq, sub, &cnt,
                                &ncnt))
     return rc;
   hipLaunchKernelGGL(k_mu_stamp, dim3((unsigned)((m_tile + kMuWG - 1) / kMuWG)), dim3(kMuWG), 0, ctx->stream, A,
@@ -475,10 +468,10 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
   P.valid = out->insert_valid;
   P.Lam = out->prop_Lambdas;
   P.th = out->prop_thetas;
-  P.et = (double*)(base + o_pet);
+  P.et = p_et;
   P.w = out->prop_weights;
-  P.col = (double*)(base + o_pcol);
-  P.src = (int32_t*)(base + o_psrc);
+  P.col = p_col;
+  P.src = p_src;
   P.n_new = n_new;
   P.stats = out->stats;
   hipLaunchKernelGGL(k_mu_plan, dim3((unsigned)na), dim3(kMuWG), plan_lds, ctx->stream, A, P);
@@ -498,7 +491,7 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
     B.sources = P.src + o;
     if (int rc = gc::insert_launch(ctx, map, (int64_t)in->h_active_dense[a] * m_tile, m_tile, &B, timestamp, scan_seq,
                                    decay_lambda, next_global_id, id_off + a, out->insert_target_slots + o,
-                                   out->new_ids + o, base + o_sub,
+                                   out->new_ids + o, sub,
                                    out->stats + GC_MAP_UPDATE_STATS_HEAD + GC_MAP_UPDATE_STATS_TILE * a))
       return rc;
   }

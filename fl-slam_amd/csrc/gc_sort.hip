@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gc_internal.h"
 #include "gc_sort.h"
 
 namespace gc {
@@ -140,28 +141,39 @@ __global__ void __launch_bounds__(kSortWG) k_sort_scatter(const uint64_t* __rest
   }
 }
 
+// the temporary block: the ping-pong keys (and values), the tile counts, the digit totals
+struct SortTemp {
+  uint64_t* kt;
+  uint32_t *vt, *hist, *totals;
+};
+SortTemp sort_layout(Carver& c, int64_t n_seg, int64_t L, bool vals) {
+  const int64_t nbs = (L + kSortTile - 1) / kSortTile, n = n_seg * L;
+  SortTemp t;
+  t.kt = c.take<uint64_t>(n);
+  t.vt = vals ? c.take<uint32_t>(n) : nullptr;
+  t.hist = c.take<uint32_t>((size_t)(n_seg * kSortDigits * nbs));
+  t.totals = c.take<uint32_t>((size_t)(n_seg * kSortDigits));
+  return t;
+}
+
 }  // namespace
 
 size_t sort_temp_bytes(int64_t n_seg, int64_t L, bool vals) {
-  const int64_t nbs = (L + kSortTile - 1) / kSortTile, n = n_seg * L;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  return al(sizeof(uint64_t) * n) + (vals ? al(sizeof(uint32_t) * n) : 0) +
-         al(sizeof(uint32_t) * (size_t)(n_seg * kSortDigits * nbs)) + al(sizeof(uint32_t) * (size_t)(n_seg * kSortDigits));
+  Carver c;
+  sort_layout(c, n_seg, L, vals);
+  return c.bytes;
 }
 
 hipError_t radix_sort_pairs(hipStream_t st, const double* keys_in, double* keys_out, const uint32_t* vals_in,
                             uint32_t* vals_out, int64_t n_seg, int64_t L, bool descending, void* temp) {
   if (n_seg <= 0 || L <= 0) return hipSuccess;
   if (n_seg * L >= ((int64_t)1 << 32) || L >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
-  const int64_t nbs = (L + kSortTile - 1) / kSortTile, n = n_seg * L;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const int64_t nbs = (L + kSortTile - 1) / kSortTile;
   const bool vals = vals_in != nullptr;
-  char* p = (char*)temp;
-  uint64_t* kt = (uint64_t*)p; p += al(sizeof(uint64_t) * n);
-  uint32_t* vt = nullptr;
-  if (vals) { vt = (uint32_t*)p; p += al(sizeof(uint32_t) * n); }
-  uint32_t* hist = (uint32_t*)p; p += al(sizeof(uint32_t) * (size_t)(n_seg * kSortDigits * nbs));
-  uint32_t* totals = (uint32_t*)p;
+  Carver c{(char*)temp};
+  const SortTemp t = sort_layout(c, n_seg, L, vals);
+  uint64_t* kt = t.kt;
+  uint32_t *vt = t.vt, *hist = t.hist, *totals = t.totals;
   const unsigned tiles = (unsigned)(n_seg * nbs), scans = (unsigned)(n_seg * kSortDigits);
   for (int pass = 0; pass < kSortPasses; ++pass) {
     const int shift = 8 * pass;

@@ -31,13 +31,14 @@
 // Masked points (a coordinate at or beyond 0.1 x the non-finite sentinel, or NaN) take no part in
 // any sum: the reference multiplies them by a zero weight, which is the same for finite values.
 #include <hip/hip_runtime.h>
+#include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
 
 namespace gc {
 namespace {
 
-constexpr int kSfT = 256;                     // threads per workgroup (centre, keys, scan, scatter)
+constexpr int kSfT = 256;                    // threads per workgroup (centre, keys, scan, scatter)
 constexpr int kSfMaxGrid = 256;               // centre workgroups
 constexpr int kSfTile = 1024;                 // points per ranking tile
 constexpr int kSfRounds = kSfTile / kSfT;
@@ -74,37 +75,17 @@ __global__ void __launch_bounds__(kSfT) k_sf_center(int64_t N, const double* __r
       a[3] += wi;
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    double x = a[q];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    if (lane == 0) red[wv * 4 + q] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double t = 0.0;
-    for (int u = 0; u < kSfT / 64; ++u) t += red[u * 4 + threadIdx.x];
-    partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
-  }
+  block_sum_stage<4>(a, red);
+  if (threadIdx.x < 4)
+    partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = block_sum_total<4, kSfT / 64>(red, threadIdx.x);
 }
 
-// center = Σ p w / (Σ w + eig_min) (lidar_surfel_extraction.py:265-266) from the G partials, by the 256
-// threads of a workgroup in an order that depends on G alone: thread (c, q) adds value q of the
-// workgroups c, c + 64, ...; the 64 chains are then added in the order c = 0..63. cen (LDS, 3) on return.
+// center = Σ p w / (Σ w + eig_min) (lidar_surfel_extraction.py:265-266) from the G partials, added by the
+// 256 threads of a workgroup in an order that depends on G alone (sum_partials: 4 columns, 64 chains).
+// cen (LDS, 3) on return.
 GC_DEV void sf_center(int G, const double* __restrict__ partial, double eig_min, double* stage /* kSfT */,
                       double* cen /* 4 */) {
-  const int q = threadIdx.x & 3, c = threadIdx.x >> 2;
-  double t = 0.0;
-  for (int b = c; b < G; b += kSfT / 4) t += partial[(int64_t)b * 4 + q];
-  stage[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double x = 0.0;
-    for (int cc = 0; cc < kSfT / 4; ++cc) x += stage[cc * 4 + threadIdx.x];
-    cen[threadIdx.x] = x;
-  }
-  __syncthreads();
+  sum_partials<4, kSfT>(G, partial, 4, stage, cen);
   const double den = cen[3] + eig_min;
   __syncthreads();
   if (threadIdx.x < 3) cen[threadIdx.x] = cen[threadIdx.x] / den;
@@ -241,8 +222,7 @@ __global__ void __launch_bounds__(kSfFitT) k_sf_fit(int64_t N, const double* __r
     a1[4] += ts[i];
   }
 #pragma unroll
-  for (int q = 0; q < 5; ++q)
-    for (int off = kSfFitLanes / 2; off >= 1; off >>= 1) a1[q] += __shfl_xor(a1[q], off, 64);
+  for (int q = 0; q < 5; ++q) a1[q] = group_sum_xor<kSfFitLanes>(a1[q]);
   const double ws = a1[0], st = a1[4];
   const double w_sum = ws + kSfEps;
   const double mu[3] = {a1[1] / w_sum, a1[2] / w_sum, a1[3] / w_sum};
@@ -258,8 +238,7 @@ __global__ void __launch_bounds__(kSfFitT) k_sf_fit(int64_t N, const double* __r
     a2[3] += wi * dy * dy; a2[4] += wi * dy * dz; a2[5] += wi * dz * dz;
   }
 #pragma unroll
-  for (int q = 0; q < 6; ++q)
-    for (int off = kSfFitLanes / 2; off >= 1; off >>= 1) a2[q] += __shfl_xor(a2[q], off, 64);
+  for (int q = 0; q < 6; ++q) a2[q] = group_sum_xor<kSfFitLanes>(a2[q]);
   const double cxx = a2[0], cxy = a2[1], cxz = a2[2], cyy = a2[3], cyz = a2[4], czz = a2[5];
   const double Cr[9] = {cxx / w_sum, cxy / w_sum, cxz / w_sum, cxy / w_sum, cyy / w_sum,
                         cyz / w_sum, cxz / w_sum, cyz / w_sum, czz / w_sum};
@@ -347,7 +326,7 @@ __global__ void __launch_bounds__(kSfWriteT) k_sf_write(int n_cells, const int32
   const int first = blockIdx.x * kSfWriteT, c = first + t;
   int before = 0;
   for (int j = t; j < first; j += kSfWriteT) before += flag[j];
-  for (int off = 32; off >= 1; off >>= 1) before += __shfl_xor(before, off, 64);
+  before = group_sum_xor<64>(before);
   const int f = c < n_cells ? flag[c] : 0;
   int x = f;
 #pragma unroll
@@ -445,25 +424,23 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
   const int G = (int)(blocks < 1 ? 1 : (blocks > kSfMaxGrid ? kSfMaxGrid : blocks));
   const int64_t tiles64 = (N + kSfTile - 1) / kSfTile;
   const int n_tiles = (int)(tiles64 < 1 ? 1 : tiles64);
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t npt = (size_t)(N > 0 ? N : 1);
-  const size_t bpart = al(sizeof(double) * 4 * G), bcen = al(sizeof(double) * 4), bkey = al(sizeof(int32_t) * npt),
-               bhist = al(sizeof(uint32_t) * (size_t)n_tiles * n_cells), bcnt = al(sizeof(int32_t) * n_cells),
-               bbuck = al(sizeof(int32_t) * (size_t)n_cells * cfg.max_occ),
-               brec = al(sizeof(double) * kSfRec * (size_t)n_cells), bnv = al(sizeof(int32_t));
-  void* scr;
-  if (int rc = gc::scratch(ctx, bpart + bcen + 2 * bkey + bhist + 2 * bcnt + bbuck + brec + bnv, &scr)) return rc;
-  char* p = (char*)scr;
-  double* partial = (double*)p; p += bpart;
-  double* center = (double*)p; p += bcen;
-  int32_t* keys = (int32_t*)p; p += bkey;
-  int32_t* trank = (int32_t*)p; p += bkey;
-  uint32_t* hist = (uint32_t*)p; p += bhist;
-  int32_t* count = (int32_t*)p; p += bcnt;
-  int32_t* flag = (int32_t*)p; p += bcnt;
-  int32_t* bucket = (int32_t*)p; p += bbuck;
-  double* rec = (double*)p; p += brec;
-  int32_t* d_nv = (int32_t*)p;
+  double *partial, *center, *rec;
+  int32_t *keys, *trank, *count, *flag, *bucket, *d_nv;
+  uint32_t* hist;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        partial = c.take<double>(4 * (size_t)G);
+        center = c.take<double>(4);
+        keys = c.take<int32_t>(npt);
+        trank = c.take<int32_t>(npt);
+        hist = c.take<uint32_t>((size_t)n_tiles * n_cells);
+        count = c.take<int32_t>(n_cells);
+        flag = c.take<int32_t>(n_cells);
+        bucket = c.take<int32_t>((size_t)n_cells * cfg.max_occ);
+        rec = c.take<double>(kSfRec * (size_t)n_cells);
+        d_nv = c.take<int32_t>(1);
+      }))
+    return rc;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_sf_center, dim3((unsigned)G), dim3(kSfT), 0, st, N, d_points, d_weights, partial);
   GC_LAUNCH_CHECK(ctx);

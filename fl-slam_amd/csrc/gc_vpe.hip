@@ -14,7 +14,7 @@
 //                  together), collapses them to one 128-B record [Λ_i (9) | m_i (3) | s_i | c̄_i (3)]
 //                  and accumulates the pose-independent sums (kQ values, below).
 //  k_vpe_hyp       one workgroup per hypothesis adds the per-workgroup partials in a fixed order
-//                  (vpe_sum_partials; k_vpe_totals does only that when H = 0) and streams the N
+//                  (sum_partials; k_vpe_totals does only that when H = 0) and streams the N
 //                  records (shared by all H, L2-resident):
 //                    h_trans    = A − Σ_i s_i Λ_i R m_i
 //                    cost_trans = V + Σ_i s_i yᵀ Λ_i y,  y = c̄_i/s_i − R m_i − t
@@ -23,10 +23,10 @@
 //                  the 22 x 22 embedding.
 //
 // Reproducibility: no floating-point atomics anywhere. Every sum is lane-local in index order, then
-// an xor butterfly inside the wave, then the waves of a workgroup in wave order, then the
-// workgroups in the order of vpe_sum_partials; the grid depends on N alone, so a result is bitwise
-// the same from run to run and row h of a batch equals the single-pose call.
+// the fixed-order sums of gc_blocksum.h (group_sum_xor, block_sum, sum_partials); the grid depends on N
+// alone, so a result is bitwise the same from run to run and row h of a batch equals the single-pose call.
 #include <hip/hip_runtime.h>
+#include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
 
@@ -43,24 +43,9 @@ constexpr int kRec = 16;                // doubles per row record (one 128-B lin
 // pose-independent sums: L_trans (9, no lift) | S (9) | W | A (3) | V | Σ row_masses | n_valid_meas | n_valid_map
 constexpr int kQ = 26;
 constexpr int qL = 0, qS = 9, qW = 18, qA = 19, qV = 22, qM = 23, qNv = 24, qNm = 25;
-static_assert(kQ <= 32, "vpe_sum_partials gives each value one of 32 thread columns");
-
-// sum of v[0..NV) over the workgroup in a fixed order; thread q < NV returns the total of value q in out
-template <int NV>
-GC_DEV void vpe_block_sum(double (&v)[NV], double* red /* (kVpeT / 64) * NV */) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double x = v[q];
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-    v[q] = x;
-  }
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int q = 0; q < NV; ++q) red[wv * NV + q] = v[q];
-  __syncthreads();
-}
+// the second pass (sum_partials) gives each value one of 32 thread columns: eight chains of workgroups
+constexpr int kVpeCols = 32;
+static_assert(kQ <= kVpeCols, "one thread column per value");
 
 __global__ void __launch_bounds__(kVpeT) k_vpe_collapse(
     int64_t N, int K, int L, const double* __restrict__ Lam, const double* __restrict__ tht,
@@ -111,8 +96,7 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_collapse(
     double g[4] = {pi[0] + pi[1], pi[0] * c[0][0] + pi[1] * c[1][0], pi[0] * c[0][1] + pi[1] * c[1][1],
                    pi[0] * c[0][2] + pi[1] * c[1][2]};
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      for (int off = kVpeGroup / 2; off >= 1; off >>= 1) g[q] += __shfl_xor(g[q], off, 64);
+    for (int q = 0; q < 4; ++q) g[q] = group_sum_xor<kVpeGroup>(g[q]);
     const double s = g[0];
     if (vi) {
       const bool has = s != 0.0;
@@ -163,40 +147,17 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_collapse(
   // valid view entries (integers held in f64: exact)
   for (int64_t v = (int64_t)blockIdx.x * kVpeT + threadIdx.x; v < V; v += (int64_t)gridDim.x * kVpeT)
     acc[qNm] += vvalid[v] != 0 ? 1.0 : 0.0;
-  vpe_block_sum<kQ>(acc, red);
-  if ((int)threadIdx.x < kQ) {
-    double t = 0.0;
-    for (int w = 0; w < kVpeT / 64; ++w) t += red[w * kQ + threadIdx.x];
-    partial[(int64_t)blockIdx.x * kQ + threadIdx.x] = t;
-  }
+  block_sum_stage<kQ>(acc, red);
+  if ((int)threadIdx.x < kQ)
+    partial[(int64_t)blockIdx.x * kQ + threadIdx.x] = block_sum_total<kQ, kVpeT / 64>(red, threadIdx.x);
 }
 
-// Fixed-order total of the G per-workgroup partials by the kVpeT threads of one workgroup: thread
-// (c, q) sums value q over the workgroups b = c, c + 8, ... (eight independent chains keep the loads
-// in flight), then the chains are added in the order c = 0..7. tot (LDS, kQ values) holds the result
-// on return. The order depends on G alone, so k_vpe_totals and k_vpe_hyp get the same bits.
-GC_DEV void vpe_sum_partials(int G, const double* __restrict__ partial, double* stage /* kVpeT */, double* tot) {
-  const int q = threadIdx.x & 31, c = threadIdx.x >> 5;
-  double t = 0.0;
-  if (q < kQ) {
-#pragma unroll 4
-    for (int b = c; b < G; b += kVpeT / 32) t += partial[(int64_t)b * kQ + q];
-  }
-  stage[threadIdx.x] = t;
-  __syncthreads();
-  if ((int)threadIdx.x < kQ) {
-    double x = 0.0;
-    for (int cc = 0; cc < kVpeT / 32; ++cc) x += stage[cc * 32 + threadIdx.x];
-    tot[threadIdx.x] = x;
-  }
-  __syncthreads();
-}
-
-// H = 0: the totals alone (the certificate vector)
+// H = 0: the totals alone (the certificate vector). sum_partials' order depends on G alone, so this
+// kernel and k_vpe_hyp get the same bits.
 __global__ void __launch_bounds__(kVpeT) k_vpe_totals(int G, const double* __restrict__ partial, double* __restrict__ tot_out) {
   __shared__ double stage[kVpeT];
   __shared__ double tot[kQ];
-  vpe_sum_partials(G, partial, stage, tot);
+  sum_partials<kVpeCols, kVpeT>(G, partial, kQ, stage, tot);
   if ((int)threadIdx.x < kQ) tot_out[threadIdx.x] = tot[threadIdx.x];
 }
 
@@ -210,7 +171,7 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_hyp(int64_t N, const double* __re
   __shared__ double red[(kVpeT / 64) * 4];
   __shared__ double out[GC_VPE_PARTS];
   const int h = blockIdx.x;
-  vpe_sum_partials(G, partial, stage, tot);  // every hypothesis sums the partials itself: no launch between
+  sum_partials<kVpeCols, kVpeT>(G, partial, kQ, stage, tot);  // every hypothesis sums the partials itself: no launch between
   if (h == 0 && (int)threadIdx.x < kQ) tot_out[threadIdx.x] = tot[threadIdx.x];  // for the host's certificate
   const bool empty = tot[qNv] == 0.0 || tot[qNm] == 0.0;  // visual_pose_evidence.py:297-318
   double R[9];
@@ -237,17 +198,11 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_hyp(int64_t N, const double* __re
       }
     }
   }
-  vpe_block_sum<4>(acc, red);
+  block_sum<4, kVpeT / 64>(acc, red);
   if (threadIdx.x == 0) {
     if (empty) {
       for (int q = 0; q < GC_VPE_PARTS; ++q) out[q] = 0.0;
     } else {
-      double sum[4];
-      for (int q = 0; q < 4; ++q) {
-        double x = 0.0;
-        for (int w = 0; w < kVpeT / 64; ++w) x += red[w * 4 + q];
-        sum[q] = x;
-      }
       double S[9], U[9], sv[3], Vm[9], Rsc[9], Rd[9], rv[3];
       double rs = 0.0;
       for (int q = 0; q < 9; ++q) {
@@ -255,7 +210,7 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_hyp(int64_t N, const double* __re
         rs += R[q] * S[q];
         out[q] = tot[qL + q] + ((q % 4 == 0) ? eps_lift : 0.0);
       }
-      for (int q = 0; q < 3; ++q) out[9 + q] = tot[qA + q] - sum[q];
+      for (int q = 0; q < 3; ++q) out[9 + q] = tot[qA + q] - acc[q];
       svd3(S, U, sv, Vm);
       mat3_mul_nt(U, Vm, Rsc);
       if (det3(Rsc) < 0.0) {  // U diag(1, 1, -1) Vᵀ
@@ -269,7 +224,7 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_hyp(int64_t N, const double* __re
         out[12 + 4 * q] = sv[q] + eps_lift;
         out[21 + q] = (sv[q] + eps_lift) * rv[q];
       }
-      out[24] = tot[qV] + sum[3];
+      out[24] = tot[qV] + acc[3];
       out[25] = tot[qW] - rs;
     }
   }
@@ -319,15 +274,13 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
   GC_CHECK_ARG(ctx, view->positions && view->directions && view->kappas && view->valid_mask, "NULL view field");
   const int64_t tiles = (N + kVpeRows - 1) / kVpeRows;
   const int G = (int)(tiles < 1 ? 1 : (tiles > kVpeMaxGrid ? kVpeMaxGrid : tiles));
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t brec = al(sizeof(double) * kRec * (size_t)(N > 0 ? N : 1)), bpart = al(sizeof(double) * kQ * G),
-               btot = al(sizeof(double) * kQ);
-  void* scr;
-  if (int rc = gc::scratch(ctx, brec + bpart + btot, &scr)) return rc;
-  char* p = (char*)scr;
-  double* rec = (double*)p; p += brec;
-  double* partial = (double*)p; p += bpart;
-  double* tot = (double*)p;
+  double *rec, *partial, *tot;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        rec = c.take<double>(kRec * (size_t)(N > 0 ? N : 1));
+        partial = c.take<double>((size_t)kQ * G);
+        tot = c.take<double>(kQ);
+      }))
+    return rc;
   hipLaunchKernelGGL(k_vpe_collapse, dim3((unsigned)G), dim3(kVpeT), 0, ctx->stream, N, (int)K, (int)n_lobes,
                      d_Lambdas, d_thetas, d_etas, d_valid, d_resp, d_pool_idx, d_row_masses,
                      (const double*)view->positions, (const double*)view->directions, (const double*)view->kappas,
