@@ -14,7 +14,13 @@
 // exactly as jax.lax.sort / jnp.argsort do. The greedy disjoint-pair selection of merge-reduce is
 // inherently sequential and runs on one lane over the sorted candidates, stopping at the first
 // distance >= threshold.
+//
+// gc_primitive_map_maintain (backend/pipeline.py:1412-1447) runs cull, forget and merge-reduce over
+// all active tiles with no host wait: the same per-slot bodies with the tile in the grid, the
+// entries' host decisions as per-tile predicates in device memory, one segmented sort per phase.
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <vector>
 #include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
@@ -27,6 +33,7 @@ namespace {
 
 constexpr int kMaxLobesOps = 8;
 constexpr int kPartBlocks = 240;  // grid of the reduction passes (<= one wave of workgroups)
+constexpr int64_t kMaintainGroupTiles = GC_MAP_MAINTAIN_GROUP_TILES;
 
 struct Tile {
   gc_primitive_map m;
@@ -91,19 +98,24 @@ __global__ void __launch_bounds__(256) k_recency(Tile T, int64_t seq, double lam
   block_partials<3>(acc, part);
 }
 
+// one slot's terms of [n_valid, n_below, mass_below, Σ w (all slots)]; returns whether the slot is culled at thr
+GC_DEV bool cull_count_slot(const Tile& T, int64_t s, double thr, double (&acc)[4]) {
+  const int64_t g = T.s0 + s;
+  const double w = mW(T.m, g);
+  const bool valid = mValid(T.m, g) != 0;
+  const bool below = valid && w < thr;
+  acc[0] += valid ? 1.0 : 0.0;
+  acc[1] += below ? 1.0 : 0.0;
+  acc[2] += w * (below ? 1.0 : 0.0);
+  acc[3] += w;
+  return below;
+}
+
 // part: [n_valid, n_below, mass_below, Σ w (all slots)]
 __global__ void __launch_bounds__(256) k_cull_count(Tile T, double thr, double* part) {
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t g = T.s0 + s;
-    const double w = mW(T.m, g);
-    const bool valid = mValid(T.m, g) != 0;
-    const bool below = valid && w < thr;
-    acc[0] += valid ? 1.0 : 0.0;
-    acc[1] += below ? 1.0 : 0.0;
-    acc[2] += w * (below ? 1.0 : 0.0);
-    acc[3] += w;
-  }
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x)
+    cull_count_slot(T, s, thr, acc);
   block_partials<4>(acc, part);
 }
 
@@ -202,15 +214,18 @@ __global__ void __launch_bounds__(256) k_insert_apply(Tile T, gc_insert_batch B,
 
 // ---- merge-reduce
 // μ = solve(Λ + εI, θ), Σ = inv(Λ + εI), det Σ (primitive_map.py:1908-1911)
-__global__ void k_merge_prep(Tile T, double eps_lift, double* mu, double* Sig, double* dets) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= T.n) return;
+GC_DEV void merge_prep_slot(const Tile& T, int64_t s, double eps_lift, double* mu, double* Sig, double* dets) {
   const int64_t g = T.s0 + s;
   double Lr[9];
   for (int q = 0; q < 9; ++q) Lr[q] = mLam(T.m, g)[q] + ((q % 4 == 0) ? eps_lift : 0.0);
   solve3(Lr, mTh(T.m, g), mu + 3 * s);
   inv3(Lr, Sig + 9 * s);
   dets[s] = det3(Sig + 9 * s);
+}
+
+__global__ void k_merge_prep(Tile T, double eps_lift, double* mu, double* Sig, double* dets) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < T.n) merge_prep_slot(T, s, eps_lift, mu, Sig, dets);
 }
 
 // pair p of jnp.triu_indices(n, k=1) (row-major, i < j)
@@ -225,11 +240,9 @@ GC_DEV void triu_pair(int64_t n, int64_t p, int64_t* i, int64_t* j) {
   *j = p - off(r) + r + 1;
 }
 
-// Bhattacharyya distance of pair p (primitive_map.py:1921-1930)
-__global__ void k_merge_dist(Tile T, int64_t P, const double* __restrict__ mu, const double* __restrict__ Sig,
-                             const double* __restrict__ dets, double eps_lift, double* keys, uint32_t* vals) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
+// Bhattacharyya distance of pair p (primitive_map.py:1921-1930), +inf unless both slots are valid
+GC_DEV double merge_pair_dist(const Tile& T, int64_t p, const double* __restrict__ mu, const double* __restrict__ Sig,
+                              const double* __restrict__ dets, double eps_lift) {
   int64_t i, j;
   triu_pair(T.n, p, &i, &j);
   double S[9], Sr[9], Si[9];
@@ -243,14 +256,20 @@ __global__ void k_merge_dist(Tile T, int64_t P, const double* __restrict__ mu, c
   const double quad = 0.125 * dot3(rv, dm);
   const double logt = 0.5 * log(detS / sqrt(dets[i] * dets[j] + 1e-24));
   const bool pv = mValid(T.m, T.s0 + i) && mValid(T.m, T.s0 + j);
-  keys[p] = pv ? quad + logt : INFINITY;
+  return pv ? quad + logt : INFINITY;
+}
+
+__global__ void k_merge_dist(Tile T, int64_t P, const double* __restrict__ mu, const double* __restrict__ Sig,
+                             const double* __restrict__ dets, double eps_lift, double* keys, uint32_t* vals) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  keys[p] = merge_pair_dist(T, p, mu, Sig, dets, eps_lift);
   vals[p] = (uint32_t)p;
 }
 
-// greedy disjoint selection over the sorted candidates (_merge_reduce_jax select_body)
-__global__ void k_merge_select(int64_t n, int64_t P, const double* __restrict__ keys, const uint32_t* __restrict__ vals,
-                               double thr, int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// greedy disjoint selection over the sorted candidates (_merge_reduce_jax select_body), one lane
+GC_DEV int merge_select_walk(int64_t n, int64_t P, const double* __restrict__ keys, const uint32_t* __restrict__ vals,
+                             double thr, int max_pairs, uint8_t* used, int32_t* sel) {
   int ns = 0;
   for (int64_t k = 0; k < P && ns < max_pairs; ++k) {
     const double d = keys[k];
@@ -266,16 +285,18 @@ __global__ void k_merge_select(int64_t n, int64_t P, const double* __restrict__ 
     sel[2 * ns + 1] = (int32_t)j;
     ++ns;
   }
-  *n_sel = ns;
+  return ns;
 }
 
-// moment-matched merge of each selected (disjoint) pair into slot i (_merge_reduce_jax merge_body)
-__global__ void k_merge_apply(Tile T, const double* __restrict__ mu, const double* __restrict__ Sig,
-                              const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel, double eps_psd,
-                              int max_pairs) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= max_pairs || k >= *n_sel) return;
-  const int64_t i = sel[2 * k], j = sel[2 * k + 1];
+__global__ void k_merge_select(int64_t n, int64_t P, const double* __restrict__ keys, const uint32_t* __restrict__ vals,
+                               double thr, int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  *n_sel = merge_select_walk(n, P, keys, vals, thr, max_pairs, used, sel);
+}
+
+// moment-matched merge of the pair (i, j) into slot i (_merge_reduce_jax merge_body)
+GC_DEV void merge_apply_pair(const Tile& T, const double* __restrict__ mu, const double* __restrict__ Sig, int64_t i,
+                             int64_t j, double eps_psd) {
   const int64_t gi = T.s0 + i, gj = T.s0 + j;
   const double w1 = mW(T.m, gi), w2 = mW(T.m, gj), ws = w1 + w2;
   if (!(ws > 0.0)) return;
@@ -320,6 +341,158 @@ __global__ void k_merge_apply(Tile T, const double* __restrict__ mu, const doubl
   if (lu > mUpd(T.m, gi)) mUpd(T.m, gi) = lu;
   mW(T.m, gj) = 0.0;
   mValid(T.m, gj) = 0;
+}
+
+// each selected (disjoint) pair of the tile
+__global__ void k_merge_apply(Tile T, const double* __restrict__ mu, const double* __restrict__ Sig,
+                              const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel, double eps_psd,
+                              int max_pairs) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= max_pairs || k >= *n_sel) return;
+  merge_apply_pair(T, mu, Sig, sel[2 * k], sel[2 * k + 1], eps_psd);
+}
+
+// ---- the batched pass (gc_primitive_map_maintain): the same per-slot bodies over the active tiles,
+// active tile a = the slot range [dense[a] * n, (dense[a] + 1) * n); what the per-tile entries decide
+// on the host is read here from the device statistics (kMmStats doubles per active tile)
+constexpr int kMmStats = GC_MAP_MAINTAIN_STATS_TILE;
+static_assert(kMmStats == 8, "the statistics row is written by index below");
+
+struct Tiles {
+  gc_primitive_map m;
+  int64_t n;
+  const int32_t* dense;
+};
+GC_DEV Tile tile_of(const Tiles& S, int64_t a) { return Tile{S.m, (int64_t)S.dense[a] * S.n, S.n}; }
+GC_DEV bool merge_runs(const double* __restrict__ stats, int64_t a) {
+  return stats[kMmStats * a + 7] == (double)GC_MAP_MAINTAIN_MERGE_RAN;
+}
+
+// k_cull_count with the tile in blockIdx.y and its threshold thr_a[a] (NULL: thr0); partials of tile a at
+// part + a * gridDim.x * 4, blocks and slots in k_cull_count's order. APPLY: the slot is also culled and
+// forgotten (w *= gamma) in the same visit, which no other slot's result depends on.
+template <bool APPLY>
+__global__ void __launch_bounds__(256) k_mm_cull(Tiles S, double thr0, const double* __restrict__ thr_a, double gamma,
+                                                 double* part) {
+  const Tile T = tile_of(S, blockIdx.y);
+  const double thr = thr_a ? thr_a[blockIdx.y] : thr0;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x) {
+    const bool below = cull_count_slot(T, s, thr, acc);
+    if (APPLY) {
+      if (below) mValid(T.m, T.s0 + s) = 0;
+      mW(T.m, T.s0 + s) = gamma * mW(T.m, T.s0 + s);
+    }
+  }
+  block_partials<4>(acc, part + (size_t)blockIdx.y * gridDim.x * 4);
+}
+
+// k_sum_parts per tile (blockIdx.x): out[a * NV + v]
+template <int NV>
+__global__ void k_mm_sum_parts(const double* __restrict__ part, int blocks, double* out) {
+  if ((int)threadIdx.x >= NV) return;
+  const double* p = part + (size_t)blockIdx.x * blocks * NV;
+  double s = 0.0;
+  for (int b = 0; b < blocks; ++b) s += p[b * NV + threadIdx.x];
+  out[blockIdx.x * NV + threadIdx.x] = s;
+}
+
+// k_cull_keys with the tile in blockIdx.y: keys[a * n + s]
+__global__ void k_mm_cull_keys(Tiles S, double* keys) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S.n) return;
+  const Tile T = tile_of(S, blockIdx.y);
+  keys[(int64_t)blockIdx.y * S.n + s] = mW(T.m, T.s0 + s) * (mValid(T.m, T.s0 + s) ? 1.0 : 0.0);
+}
+
+// primitive_map.py:1222-1229 per tile: sums = the count at thr0, keys = the tile's w·valid descending
+__global__ void k_mm_cull_thr(int n_active, int64_t n, const double* __restrict__ sums,
+                              const double* __restrict__ keys, double thr0, int64_t max_primitives, double* thr_a) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n_active) return;
+  const double* c = sums + 4 * a;
+  const bool top = c[0] - c[1] > (double)max_primitives && max_primitives < n;
+  thr_a[a] = top ? keys[(int64_t)a * n + max_primitives] : thr0;
+}
+
+// the cull's statistics and the merge's no-op tests (primitive_map.py:1879-1890), the valid count after the cull
+__global__ void k_mm_cull_stats(int n_active, int64_t n, const double* __restrict__ sums,
+                                const double* __restrict__ thr_a, double thr0, int max_pairs, int capped,
+                                double* stats) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n_active) return;
+  const double* c = sums + 4 * a;
+  double* st = stats + kMmStats * a;
+  const double after = c[0] - c[1];
+  st[0] = c[0];
+  st[1] = c[1];
+  st[2] = c[1] > 0.0 ? c[2] : 0.0;
+  st[3] = c[3];
+  st[4] = thr_a ? thr_a[a] : thr0;
+  st[5] = 0.0;
+  st[6] = after;
+  st[7] = (n < 2 || after < 2.0 || max_pairs <= 0) ? (double)GC_MAP_MAINTAIN_MERGE_NOOP
+          : capped                                  ? (double)GC_MAP_MAINTAIN_MERGE_CAPPED
+                                                    : (double)GC_MAP_MAINTAIN_MERGE_RAN;
+}
+
+// the group's tiles a0 .. a0 + g - 1, the tile of the group in blockIdx.y; mu / Sig / dets / used hold n
+// slots per tile, keys / vals P pairs
+__global__ void k_mm_merge_prep(Tiles S, int64_t a0, const double* __restrict__ stats, double eps_lift, double* mu,
+                                double* Sig, double* dets) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
+  if (s >= S.n || !merge_runs(stats, a0 + la)) return;
+  merge_prep_slot(tile_of(S, a0 + la), s, eps_lift, mu + 3 * la * S.n, Sig + 9 * la * S.n, dets + la * S.n);
+}
+
+__global__ void k_mm_merge_dist(Tiles S, int64_t a0, int64_t P, const double* __restrict__ stats,
+                                const double* __restrict__ mu, const double* __restrict__ Sig,
+                                const double* __restrict__ dets, double eps_lift, double* keys, uint32_t* vals) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
+  if (p >= P) return;
+  const int64_t x = la * P + p;
+  vals[x] = (uint32_t)p;
+  keys[x] = merge_runs(stats, a0 + la) ? merge_pair_dist(tile_of(S, a0 + la), p, mu + 3 * la * S.n,
+                                                         Sig + 9 * la * S.n, dets + la * S.n, eps_lift)
+                                       : INFINITY;
+}
+
+// one workgroup per tile of the group, one lane walking (k_merge_select)
+__global__ void k_mm_merge_select(int64_t n, int64_t a0, int64_t P, const double* __restrict__ stats,
+                                  const double* __restrict__ keys, const uint32_t* __restrict__ vals, double thr,
+                                  int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
+  const int64_t la = blockIdx.x;
+  if (threadIdx.x != 0 || !merge_runs(stats, a0 + la)) return;
+  n_sel[a0 + la] = merge_select_walk(n, P, keys + la * P, vals + la * P, thr, max_pairs, used + la * n,
+                                     sel + la * 2 * max_pairs);
+}
+
+__global__ void k_mm_merge_apply(Tiles S, int64_t a0, const double* __restrict__ mu, const double* __restrict__ Sig,
+                                 const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel, double eps_psd,
+                                 int max_pairs) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t la = blockIdx.y;
+  if (k >= max_pairs || k >= n_sel[a0 + la]) return;
+  const int32_t* sl = sel + la * 2 * max_pairs;
+  merge_apply_pair(tile_of(S, a0 + la), mu + 3 * la * S.n, Sig + 9 * la * S.n, sl[2 * k], sl[2 * k + 1], eps_psd);
+}
+
+__global__ void __launch_bounds__(256) k_mm_count_valid(Tiles S, double* part) {
+  const Tile T = tile_of(S, blockIdx.y);
+  double acc[1] = {0.0};
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x)
+    acc[0] += mValid(T.m, T.s0 + s) ? 1.0 : 0.0;
+  block_partials<1>(acc, part + (size_t)blockIdx.y * gridDim.x);
+}
+
+__global__ void k_mm_merge_stats(int n_active, const double* __restrict__ part, int blocks,
+                                 const int32_t* __restrict__ n_sel, double* stats) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n_active) return;
+  double s = 0.0;
+  for (int b = 0; b < blocks; ++b) s += part[(size_t)a * blocks + b];
+  stats[kMmStats * a + 5] = (double)n_sel[a];
+  stats[kMmStats * a + 6] = s;
 }
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -608,6 +781,165 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
   if (int rc = count_valid(&nv)) return rc;
   h_out2[0] = ns;
   h_out2[1] = (int64_t)nv;
+  return GC_OK;
+}
+
+int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, int32_t n_active,
+                                  const int32_t* d_active_dense, const int32_t* h_active_dense, const double* h_cfg,
+                                  int64_t max_primitives, int32_t max_pairs, int64_t max_tile_size,
+                                  int64_t max_sort_keys, double* d_stats) {
+  if (int rc = check_tile(ctx, map, 0, 0, true)) return rc;  // joins the side stream first
+  GC_CHECK_ARG(ctx, m_tile > 0 && map->m_slots % m_tile == 0, "m_tile must be > 0 and divide the map's slots");
+  GC_CHECK_ARG(ctx, n_active >= 0 && n_active <= 65535, "n_active must be in [0, 65535]");
+  if (n_active == 0) return GC_OK;
+  GC_CHECK_ARG(ctx, d_active_dense && h_active_dense && h_cfg && d_stats, "NULL argument");
+  GC_CHECK_ARG(ctx, max_sort_keys >= 0, "max_sort_keys must be >= 0");
+  const int64_t n_tiles = map->m_slots / m_tile;
+  GC_CHECK_ARG(ctx, n_active <= n_tiles, "more active tiles than the map holds");
+  {
+    std::vector<uint8_t> seen((size_t)n_tiles, 0);
+    for (int a = 0; a < n_active; ++a) {
+      const int64_t d = h_active_dense[a];
+      GC_CHECK_ARG(ctx, d >= 0 && d < n_tiles, "active dense tile outside the map");
+      GC_CHECK_ARG(ctx, !seen[(size_t)d], "duplicate active tile");
+      seen[(size_t)d] = 1;
+    }
+  }
+  const double thr0 = h_cfg[0], gamma = h_cfg[1], merge_thr = h_cfg[2], eps_psd = h_cfg[3], eps_lift = h_cfg[4];
+  const bool top = max_primitives >= 0;
+  const int64_t slots = (int64_t)n_active * m_tile;
+  GC_CHECK_ARG(ctx, !top || slots < ((int64_t)1 << 32), "max_primitives: the active tiles must hold < 2^32 slots");
+  // host-known: whether the merge launches at all, and its groups
+  const bool capped = max_tile_size > 0 && m_tile > max_tile_size;
+  const bool merge = !(m_tile < 2 || max_pairs <= 0) && !capped;
+  GC_CHECK_ARG(ctx, !merge || m_tile <= 65536, "merge-reduce tile larger than 65536 slots");
+  const int64_t P = m_tile * (m_tile - 1) / 2;
+  int64_t G = 1;
+  if (merge) {
+    const int64_t budget = std::min<int64_t>(max_sort_keys > 0 ? max_sort_keys : GC_MAP_MAINTAIN_SORT_KEYS,
+                                             ((int64_t)1 << 32) - 1);
+    G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(budget / P, kMaintainGroupTiles), n_active));
+  }
+  const unsigned nb = part_blocks(m_tile);
+
+  // one scratch for the whole call, sized before the first launch (growing it waits for the stream): the
+  // partials, sums and thresholds, then the cull's sort and the merge's group, used one after the other
+  struct CullSort {
+    double *keys_in, *keys;
+    void* tmp;
+  } cs{};
+  struct MergeGroup {
+    double *mu, *Sig, *dets, *keys_in, *keys;
+    uint32_t *vals_in, *vals;
+    uint8_t* used;
+    int32_t* sel;
+    void* tmp;
+  } mg{};
+  auto cull_layout = [&](gc::Carver& c) {
+    cs.keys_in = c.take<double>((size_t)slots);
+    cs.keys = c.take<double>((size_t)slots);
+    cs.tmp = c.take<char>(gc::sort_temp_bytes(n_active, m_tile, false));
+  };
+  auto merge_layout = [&](gc::Carver& c) {
+    mg.mu = c.take<double>(3 * (size_t)(G * m_tile));
+    mg.Sig = c.take<double>(9 * (size_t)(G * m_tile));
+    mg.dets = c.take<double>((size_t)(G * m_tile));
+    mg.keys_in = c.take<double>((size_t)(G * P));
+    mg.keys = c.take<double>((size_t)(G * P));
+    mg.vals_in = c.take<uint32_t>((size_t)(G * P));
+    mg.vals = c.take<uint32_t>((size_t)(G * P));
+    mg.used = c.take<uint8_t>((size_t)(G * m_tile));
+    mg.sel = c.take<int32_t>(2 * (size_t)G * (size_t)max_pairs);
+    mg.tmp = c.take<char>(gc::sort_temp_bytes(G, P, true));
+  };
+  gc::Carver cull_size, merge_size;
+  if (top) cull_layout(cull_size);
+  if (merge) merge_layout(merge_size);
+  double *part, *sums, *thr_a;
+  int32_t* n_sel;
+  char* sub;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
+        part = c.take<double>(4 * (size_t)nb * n_active);
+        sums = c.take<double>(4 * (size_t)n_active);
+        thr_a = c.take<double>(n_active);
+        n_sel = c.take<int32_t>(n_active);
+        sub = c.take<char>(std::max(cull_size.bytes, merge_size.bytes));
+      }))
+    return rc;
+  if (top) {
+    gc::Carver c{sub};
+    cull_layout(c);
+  }
+  if (merge) {
+    gc::Carver c{sub};
+    merge_layout(c);
+  }
+
+  // ---- the first launch; no host wait from here on
+  const Tiles S{*map, m_tile, d_active_dense};
+  const dim3 tile_grid(nb, (unsigned)n_active), per_tile(blocks_for(n_active));
+  const double* thr_dev = nullptr;
+  if (top) {  // the launches are host-known, the branch is each tile's own (k_mm_cull_thr)
+    hipLaunchKernelGGL(k_mm_cull<false>, tile_grid, dim3(256), 0, ctx->stream, S, thr0, (const double*)nullptr, gamma,
+                       part);
+    GC_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mm_sum_parts<4>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
+                       (int)nb, sums);
+    GC_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mm_cull_keys, dim3(blocks_for(m_tile), (unsigned)n_active), dim3(256), 0, ctx->stream, S,
+                       cs.keys_in);
+    GC_LAUNCH_CHECK(ctx);
+    if (gc::radix_sort_pairs(ctx->stream, cs.keys_in, cs.keys, nullptr, nullptr, n_active, m_tile, true, cs.tmp) !=
+        hipSuccess) {
+      gc::set_error(ctx, "radix sort failed");
+      return GC_ERR_RUNTIME;
+    }
+    hipLaunchKernelGGL(k_mm_cull_thr, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile, (const double*)sums,
+                       (const double*)cs.keys, thr0, max_primitives, thr_a);
+    GC_LAUNCH_CHECK(ctx);
+    thr_dev = thr_a;
+  }
+  // count at the tile's threshold, cull and forget in one streaming visit
+  hipLaunchKernelGGL(k_mm_cull<true>, tile_grid, dim3(256), 0, ctx->stream, S, thr0, thr_dev, gamma, part);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_mm_sum_parts<4>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
+                     (int)nb, sums);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_mm_cull_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile, (const double*)sums,
+                     thr_dev, thr0, (int)max_pairs, capped ? 1 : 0, d_stats);
+  GC_LAUNCH_CHECK(ctx);
+  if (!merge) return GC_OK;
+
+  GC_HIP(ctx, hipMemsetAsync(n_sel, 0, sizeof(int32_t) * (size_t)n_active, ctx->stream));
+  for (int64_t a0 = 0; a0 < n_active; a0 += G) {
+    const int64_t g = std::min<int64_t>(G, n_active - a0), gs = g * m_tile;
+    GC_HIP(ctx, hipMemsetAsync(mg.used, 0, (size_t)gs, ctx->stream));
+    hipLaunchKernelGGL(k_mm_merge_prep, dim3(blocks_for(m_tile), (unsigned)g), dim3(256), 0, ctx->stream, S, a0,
+                       (const double*)d_stats, eps_lift, mg.mu, mg.Sig, mg.dets);
+    GC_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mm_merge_dist, dim3(blocks_for(P), (unsigned)g), dim3(256), 0, ctx->stream, S, a0, P,
+                       (const double*)d_stats, (const double*)mg.mu, (const double*)mg.Sig, (const double*)mg.dets,
+                       eps_lift, mg.keys_in, mg.vals_in);
+    GC_LAUNCH_CHECK(ctx);
+    if (gc::radix_sort_pairs(ctx->stream, mg.keys_in, mg.keys, mg.vals_in, mg.vals, g, P, false, mg.tmp) !=
+        hipSuccess) {
+      gc::set_error(ctx, "radix sort failed");
+      return GC_ERR_RUNTIME;
+    }
+    hipLaunchKernelGGL(k_mm_merge_select, dim3((unsigned)g), dim3(64), 0, ctx->stream, m_tile, a0, P,
+                       (const double*)d_stats, (const double*)mg.keys, (const uint32_t*)mg.vals, merge_thr,
+                       (int)max_pairs, mg.used, mg.sel, n_sel);
+    GC_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_mm_merge_apply, dim3((unsigned)((max_pairs + 255) / 256), (unsigned)g), dim3(256), 0,
+                       ctx->stream, S, a0, (const double*)mg.mu, (const double*)mg.Sig, (const int32_t*)mg.sel,
+                       (const int32_t*)n_sel, eps_psd, (int)max_pairs);
+    GC_LAUNCH_CHECK(ctx);
+  }
+  hipLaunchKernelGGL(k_mm_count_valid, tile_grid, dim3(256), 0, ctx->stream, S, part);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_mm_merge_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, (const double*)part,
+                     (int)nb, (const int32_t*)n_sel, d_stats);
+  GC_LAUNCH_CHECK(ctx);
   return GC_OK;
 }
 

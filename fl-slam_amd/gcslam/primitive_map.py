@@ -4,7 +4,8 @@ primitive_map_fuse (:992-1163) with the world pushforward of transform_gaussian_
 primitive_map_insert_masked (:807-982), primitive_map_cull (:1175-1305), primitive_map_forget
 (:1314-1390), primitive_map_recency_inflate (:1400-1490) and primitive_map_merge_reduce
 (:1809-2030); primitive_map_update_from_association chains them as the post-pose map update of
-backend/pipeline.py:1232-1492 does (step 12b), fuse and novelty insert in one device pass. The map
+backend/pipeline.py:1232-1492 does (step 12b), fuse and novelty insert in one device pass, and
+primitive_map_maintain runs its cull / forget / merge-reduce over all active tiles in another. The map
 lives in HBM as one flat array of n_tiles * m_tile slots (tile t, local slot j -> t * m_tile + j);
 every operator runs in place on its tile. The AtlasMap bookkeeping (next_global_id, total_count,
 per-tile count) stays on the host, as in the reference."""
@@ -365,16 +366,21 @@ def primitive_map_cull(atlas_map: DevicePrimitiveMap, tile_id: int,
     _abi.call("gc_primitive_map_cull", atlas_map.ctx.handle, C.byref(atlas_map.struct()), s0, n,
               float(weight_threshold), -1 if max_primitives is None else int(max_primitives), out.ctypes.data,
               ctx=atlas_map.ctx)
-    n_culled, mass_dropped, sum_w, n_valid = int(out[0]), float(out[1]), float(out[2]), int(out[3])
+    return _cull_finish(atlas_map, int(tile_id), int(out[3]), int(out[0]), float(out[1]), float(out[2]), chart_id,
+                        anchor_id)
+
+
+def _cull_finish(atlas_map, tile_id: int, n_valid: int, n_culled: int, mass_dropped: float, sum_w: float,
+                 chart_id: str, anchor_id: str):
+    """The bookkeeping, certificate and effect of a cull from its device counts (primitive_map.py:1240-1305)."""
     if n_valid == 0 or n_culled == 0:
-        return _no_op(PrimitiveMapCullResult(atlas_map, int(tile_id), 0, 0.0), chart_id, anchor_id,
-                      "primitive_map_cull")
-    atlas_map.tile_count[int(tile_id)] = n_valid - n_culled
+        return _no_op(PrimitiveMapCullResult(atlas_map, tile_id, 0, 0.0), chart_id, anchor_id, "primitive_map_cull")
+    atlas_map.tile_count[tile_id] = n_valid - n_culled
     atlas_map.total_count -= n_culled
     cert = CertBundle.create_approx(chart_id=chart_id, anchor_id=anchor_id, triggers=["budgeting", "mass_drop"],
                                     influence=InfluenceCert.identity().with_overrides(
                                         mass_epsilon_ratio=mass_dropped / (sum_w + GC_EPS_MASS)))
-    return (PrimitiveMapCullResult(atlas_map, int(tile_id), n_culled, mass_dropped), cert,
+    return (PrimitiveMapCullResult(atlas_map, tile_id, n_culled, mass_dropped), cert,
             ExpectedEffect(objective_name="primitive_map_cull", predicted=float(n_culled), realized=float(n_culled)))
 
 
@@ -447,37 +453,50 @@ def primitive_map_merge_reduce(atlas_map: DevicePrimitiveMap, tile_id: int,
                                ) -> Tuple[PrimitiveMapMergeReduceResult, CertBundle, ExpectedEffect]:
     """primitive_map_merge_reduce (primitive_map.py:1809-2030)."""
     s0, M = atlas_map.tile_range(tile_id)
+    if int(max_tile_size) > 0 and M > int(max_tile_size):
+        # the budget cap (:1881-1890) applies after the M / valid count / max_pairs no-op test (:1879)
+        n_valid = int(atlas_map.download_tile(tile_id, "valid_mask")["valid_mask"].sum())
+        state = _MM_NOOP if M < 2 or n_valid < 2 or int(max_pairs) <= 0 else _MM_CAPPED
+        return _merge_finish(atlas_map, int(tile_id), state, 0, 0, int(max_pairs), int(max_tile_size), chart_id,
+                             anchor_id)
+    out = np.zeros(2, np.int64)
+    _abi.call("gc_primitive_map_merge_reduce", atlas_map.ctx.handle, C.byref(atlas_map.struct()), s0, M,
+              float(merge_threshold), int(max_pairs), float(eps_psd), float(eps_lift), out.ctypes.data,
+              ctx=atlas_map.ctx)
+    return _merge_finish(atlas_map, int(tile_id), _MM_RAN, int(out[0]), int(out[1]), int(max_pairs),
+                         int(max_tile_size), chart_id, anchor_id)
+
+
+_MM_RAN, _MM_NOOP, _MM_CAPPED = 0, 1, 2  # GC_MAP_MAINTAIN_MERGE_*
+
+
+def _merge_finish(atlas_map, tile_id: int, state: int, n_merged: int, count: int, max_pairs: int,
+                  max_tile_size: int, chart_id: str, anchor_id: str):
+    """The bookkeeping, certificate and effect of a merge-reduce from its outcome (primitive_map.py:1879-1890,
+    :1985-2030): the exact no-op, the budget cap, or n_merged pairs leaving `count` valid slots."""
+    M = atlas_map.m_tile
 
     def no_op(predicted, triggers=None, influence=None):
-        res = PrimitiveMapMergeReduceResult(atlas_map, int(tile_id), 0, 0.0)
+        res = PrimitiveMapMergeReduceResult(atlas_map, tile_id, 0, 0.0)
         cert = (CertBundle.create_approx(chart_id=chart_id, anchor_id=anchor_id, triggers=triggers,
                                          frobenius_applied=True, influence=influence or InfluenceCert.identity())
                 if triggers else CertBundle.create_exact(chart_id=chart_id, anchor_id=anchor_id))
         return res, cert, ExpectedEffect(objective_name="primitive_map_merge_reduce", predicted=predicted,
                                          realized=0.0)
 
-    if int(max_tile_size) > 0 and M > int(max_tile_size):
-        # the budget cap (:1881-1890) applies after the M / valid count / max_pairs no-op test (:1879)
-        n_valid = int(atlas_map.download_tile(tile_id, "valid_mask")["valid_mask"].sum())
-        if M < 2 or n_valid < 2 or int(max_pairs) <= 0:
-            return no_op(float(max_pairs))
-        over = float(M - int(max_tile_size)) / float(max(M, 1))
+    if state == _MM_CAPPED:
+        over = float(M - max_tile_size) / float(max(M, 1))
         return no_op(float(max_pairs), ["merge_reduce_budget_cap"],
                      InfluenceCert.identity().with_overrides(mass_epsilon_ratio=over))
-    out = np.zeros(2, np.int64)
-    _abi.call("gc_primitive_map_merge_reduce", atlas_map.ctx.handle, C.byref(atlas_map.struct()), s0, M,
-              float(merge_threshold), int(max_pairs), float(eps_psd), float(eps_lift), out.ctypes.data,
-              ctx=atlas_map.ctx)
-    n_merged, count = int(out[0]), int(out[1])
-    if n_merged <= 0:
+    if state == _MM_NOOP or n_merged <= 0:
         return no_op(float(max_pairs))
     atlas_map.colors_stale(tile_id)  # merged colours use max(denom, eps_psd) (primitive_map.py:1976-1983)
-    atlas_map.tile_count[int(tile_id)] = count
+    atlas_map.tile_count[tile_id] = count
     atlas_map.total_count -= n_merged
     cert = CertBundle.create_approx(chart_id=chart_id, anchor_id=anchor_id, triggers=["primitive_map_merge_reduce"],
                                     frobenius_applied=True, influence=InfluenceCert.identity().with_overrides(
                                         mass_epsilon_ratio=float(n_merged) / float(max(M, 1))))
-    return (PrimitiveMapMergeReduceResult(atlas_map, int(tile_id), n_merged, float(n_merged)), cert,
+    return (PrimitiveMapMergeReduceResult(atlas_map, tile_id, n_merged, float(n_merged)), cert,
             ExpectedEffect(objective_name="primitive_map_merge_reduce", predicted=float(max_pairs),
                            realized=float(n_merged)))
 
@@ -525,6 +544,107 @@ class MapUpdateConfig:
     max_tile_size: int = GC_PRIMITIVE_MERGE_MAX_TILE_SIZE
 
 
+_MM_TILE = 8  # GC_MAP_MAINTAIN_STATS_TILE
+
+
+@dataclass
+class PrimitiveMapMaintainResult:
+    """Cull / forget / merge-reduce of the active tiles, one entry per tile in the given order."""
+    atlas_map: DevicePrimitiveMap
+    tile_ids: List[int]
+    n_culled: np.ndarray      # (n_active,) int64
+    mass_dropped: np.ndarray  # (n_active,) float64
+    n_merged: np.ndarray      # (n_active,) int64
+    n_culled_total: int
+    mass_dropped_total: float
+    n_merged_total: int
+    tile_certs: List[Tuple[CertBundle, CertBundle, CertBundle]]  # per tile: (cull, forget, merge)
+
+
+def _maintain_check(atlas_map, dense: List[int], cfg: MapUpdateConfig) -> None:
+    """The argument errors of the batched maintenance, raised before any device call."""
+    if len(set(dense)) != len(dense):
+        raise ValueError(f"duplicate tile ids in {dense}")
+    n_tiles = len(atlas_map.tile_keys)
+    for d in dense:
+        if not 0 <= d < n_tiles:
+            raise ValueError(f"tile_id {d} outside [0, {n_tiles})")
+    if "valid_mask" not in atlas_map.ptrs:
+        raise ValueError("the map has no maintenance fields")
+    M, cap = atlas_map.m_tile, int(cfg.max_tile_size)
+    runs = M >= 2 and int(cfg.k_merge_pairs_tile) > 0 and not (cap > 0 and M > cap)
+    if runs and M > 65536:
+        raise ValueError(f"merge-reduce of tiles of {M} slots: at most 65536")
+
+
+def _maintain_launch(atlas_map, d_dense, h_dense: np.ndarray, cfg: MapUpdateConfig, max_primitives: Optional[int],
+                     max_sort_keys: int, d_stats) -> None:
+    """gc_primitive_map_maintain on the map's stream: no download, no wait."""
+    h_cfg = np.array([cfg.primitive_cull_weight_threshold, cfg.primitive_forgetting_factor,
+                      cfg.primitive_merge_threshold, cfg.eps_psd, cfg.eps_lift], np.float64)
+    _abi.call("gc_primitive_map_maintain", atlas_map.ctx.handle, C.byref(atlas_map.struct()), atlas_map.m_tile,
+              int(h_dense.shape[0]), d_dense.ptr, h_dense.ctypes.data, h_cfg.ctypes.data,
+              -1 if max_primitives is None else int(max_primitives), int(cfg.k_merge_pairs_tile),
+              int(cfg.max_tile_size), int(max_sort_keys), d_stats.ptr, ctx=atlas_map.ctx)
+
+
+def _maintain_finish(atlas_map, dense: List[int], stats: np.ndarray, cfg: MapUpdateConfig, chart_id: str
+                     ) -> PrimitiveMapMaintainResult:
+    """The bookkeeping and the certificates the loop of per-tile operators would have left, from the
+    statistics of the one pass (tiles in order; cull, forget, merge of each)."""
+    st = np.asarray(stats, np.float64).reshape(len(dense), _MM_TILE)
+    n_culled, mass, n_merged, certs = [], [], [], []
+    for a, d in enumerate(dense):
+        rc, cc, _ = _cull_finish(atlas_map, d, int(st[a, 0]), int(st[a, 1]), float(st[a, 2]), float(st[a, 3]),
+                                 chart_id, "primitive_map")
+        cf = CertBundle.create_exact(chart_id=chart_id, anchor_id="primitive_map")
+        rm, cm, _ = _merge_finish(atlas_map, d, int(st[a, 7]), int(st[a, 5]), int(st[a, 6]),
+                                  int(cfg.k_merge_pairs_tile), int(cfg.max_tile_size), chart_id,
+                                  "primitive_map_merge_reduce")
+        n_culled.append(int(rc.n_culled))
+        mass.append(float(rc.mass_dropped))
+        n_merged.append(int(rm.n_merged))
+        certs.append((cc, cf, cm))
+    evicted = 0.0
+    for m in mass:  # summed in tile order, as the loop does
+        evicted += m
+    return PrimitiveMapMaintainResult(
+        atlas_map=atlas_map, tile_ids=list(dense), n_culled=np.asarray(n_culled, np.int64),
+        mass_dropped=np.asarray(mass, np.float64), n_merged=np.asarray(n_merged, np.int64),
+        n_culled_total=int(sum(n_culled)), mass_dropped_total=evicted, n_merged_total=int(sum(n_merged)),
+        tile_certs=certs)
+
+
+def primitive_map_maintain(atlas_map: DevicePrimitiveMap, tile_ids, config: Optional[MapUpdateConfig] = None,
+                           max_primitives: Optional[int] = None, max_sort_keys: int = 0,
+                           chart_id: str = GC_CHART_ID
+                           ) -> Tuple[PrimitiveMapMaintainResult, CertBundle, ExpectedEffect]:
+    """The maintenance of step 12b (pipeline.py:1412-1447) over the dense tiles `tile_ids` in one device
+    pass (gc_primitive_map_maintain) and one download: per tile primitive_map_cull, primitive_map_forget
+    and primitive_map_merge_reduce (anchor "primitive_map_merge_reduce"), with the map, the bookkeeping
+    and the certificates the loop of those operators leaves. max_sort_keys bounds the merge's scratch
+    (pair keys sorted at once; 0 = the library's default)."""
+    from .certificates import aggregate_certificates
+    cfg = config or MapUpdateConfig()
+    dense = [int(t) for t in tile_ids]
+    _maintain_check(atlas_map, dense, cfg)
+    predicted = float(len(dense) * int(cfg.k_merge_pairs_tile))
+    if not dense:
+        z = np.zeros(0)
+        return (PrimitiveMapMaintainResult(atlas_map, [], z.astype(np.int64), z, z.astype(np.int64), 0, 0.0, 0, []),
+                CertBundle.create_exact(chart_id=chart_id, anchor_id="primitive_map"),
+                ExpectedEffect(objective_name="primitive_map_maintain", predicted=0.0, realized=0.0))
+    ctx = atlas_map.ctx
+    h_dense = np.asarray(dense, np.int32)
+    d_dense, = _abi.upload_many(ctx, [h_dense], [np.int32])
+    d_stats = _abi.DeviceArray(ctx, (len(dense) * _MM_TILE,), np.float64)
+    _maintain_launch(atlas_map, d_dense, h_dense, cfg, max_primitives, max_sort_keys, d_stats)
+    res = _maintain_finish(atlas_map, dense, d_stats.download(), cfg, chart_id)  # the one download
+    cert = aggregate_certificates([c for t in res.tile_certs for c in t])
+    return res, cert, ExpectedEffect(objective_name="primitive_map_maintain", predicted=predicted,
+                                     realized=float(res.n_merged_total))
+
+
 @dataclass
 class PrimitiveMapUpdateResult:
     """The counters of pipeline.py:930-937 and the insert plan, one row per active tile."""
@@ -551,7 +671,7 @@ def _mu_shape(x):
 def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, association_result, measurement_batch,
                                           active_tile_ids, pose_world, timestamp: float, scan_seq: int,
                                           config: Optional[MapUpdateConfig] = None,
-                                          map_branch_stats: Optional[dict] = None, maintenance: bool = True,
+                                          map_branch_stats: Optional[dict] = None, maintenance=True,
                                           event_log: bool = False, chart_id: str = GC_CHART_ID
                                           ) -> Tuple[PrimitiveMapUpdateResult, CertBundle, ExpectedEffect]:
     """Step 12b of the reference (backend/pipeline.py:1232-1492) with z_t = pose_world = [t, rotvec]:
@@ -561,7 +681,10 @@ def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, associa
     ma_hex_stencil_tile_ids order. The fuse and the inserts run in one device pass
     (gc_primitive_map_update) with one download at its end; the association's and the batch's
     `.device` arrays are read in place, host arrays are uploaded. map_branch_stats: the six floats
-    the map branch hands to the certificate (pipeline.py:920-925)."""
+    the map branch hands to the certificate (pipeline.py:920-925). maintenance: False skips cull /
+    forget / merge-reduce, True runs them through the per-tile operators (each waits for its counts),
+    "device" chains gc_primitive_map_maintain behind the update on the same stream, its statistics
+    in the same download: all of step 12b in one pass and one wait, with the same results."""
     cfg = config or MapUpdateConfig()
     ctx = atlas_map.ctx
     keys = [int(t) for t in active_tile_ids]
@@ -613,6 +736,11 @@ def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, associa
         raise ValueError(f"block_size must be >= 1, got {cfg.block_size}")
     if "valid_mask" not in atlas_map.ptrs:
         raise ValueError("the map has no maintenance fields")
+    on_device = isinstance(maintenance, str)
+    if on_device:
+        if maintenance != "device":
+            raise ValueError(f"maintenance must be True, False or 'device', got {maintenance!r}")
+        _maintain_check(atlas_map, dense, cfg)
     mb = dict(map_branch_stats or {})
     L = atlas_map.n_lobes
     AK = n_active * k_ins
@@ -629,18 +757,21 @@ def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, associa
         d_in = _abi.upload_many(ctx, host_in, dts)
         d_out = _abi.alloc_many(ctx, [((AK,), np.int32), ((AK,), np.uint8), ((AK,), np.int32), ((AK,), np.int64),
                                       ((AK, 9), np.float64), ((AK, 3), np.float64), ((AK,), np.float64),
-                                      ((n_stats,), np.float64)])
+                                      ((n_stats,), np.float64)] +
+                                ([((n_active * _MM_TILE,), np.float64)] if on_device else []))
         s_in = _MapUpdateIn(N, m_tile, K, n_active, k_ins, int(cfg.block_size), *[d.ptr for d in d_in],
                             h_dense.ctypes.data)
-        s_out = _MapUpdateOut(*[d.ptr for d in d_out])
+        s_out = _MapUpdateOut(*[d.ptr for d in d_out[:8]])
         h_cfg = np.array([cfg.eps_lift, cfg.eps_mass, cfg.h_tile, cfg.recency_decay_lambda], np.float64)
         _abi.call("gc_primitive_map_update", ctx.handle, C.byref(atlas_map.struct()), C.byref(s_in), pose.ctypes.data,
                   h_cfg.ctypes.data, float(timestamp), int(scan_seq), int(atlas_map.next_global_id), C.byref(s_out),
                   ctx=ctx)
-        idx, val, slots, ids, pL, pth, pw, stats = _abi.download_many(d_out)  # the one download
+        if on_device:  # behind the last insert, on the same stream
+            _maintain_launch(atlas_map, d_in[-1], h_dense, cfg, None, 0, d_out[8])
+        idx, val, slots, ids, pL, pth, pw, stats, *mstats = _abi.download_many(d_out)  # the one download
     else:
         idx, val, slots, ids = (np.zeros(0, t) for t in (np.int32, np.uint8, np.int32, np.int64))
-        pL, pth, pw, stats = np.zeros((0, 9)), np.zeros((0, 3)), np.zeros(0), np.zeros(n_stats)
+        pL, pth, pw, stats, mstats = np.zeros((0, 9)), np.zeros((0, 3)), np.zeros(0), np.zeros(n_stats), [np.zeros(0)]
     tiles = stats[_MU_HEAD:].reshape(n_active, _MU_TILE)
     n_fused = n_active * int(stats[1])
     n_inserted, mass_total, mass_p95 = 0, 0.0, 0.0
@@ -669,7 +800,10 @@ def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, associa
                 entries.append({"tile_id": keys[a], "mu_world": mu[q].tolist(), "weight": float(pw[sl][q]),
                                 "color": col[idx[sl][q]].tolist(), "timestamp": float(timestamp)})
     n_culled, n_merged, evicted = 0, 0, 0.0
-    if maintenance:  # pipeline.py:1412-1447, per active tile in order
+    if on_device:  # pipeline.py:1412-1447 from the pass's statistics
+        mr = _maintain_finish(atlas_map, dense, mstats[0], cfg, chart_id)
+        n_culled, n_merged, evicted = mr.n_culled_total, mr.n_merged_total, mr.mass_dropped_total
+    elif maintenance:  # pipeline.py:1412-1447, per active tile in order
         for d in dense:
             rc, _, _ = primitive_map_cull(atlas_map, d, cfg.primitive_cull_weight_threshold, chart_id=chart_id)
             n_culled += int(rc.n_culled)

@@ -854,6 +854,45 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
                                 const double* h_pose6, const double* h_cfg, double timestamp, int64_t scan_seq,
                                 int64_t next_global_id, const gc_map_update_out* out);
 
+/* The maintenance of step 12b (backend/pipeline.py:1412-1447) over all active tiles in one pass:
+   per active tile primitive_map_cull (primitive_map.py:1175-1305), primitive_map_forget (:1314-1390)
+   and primitive_map_merge_reduce (:1809-2030), with the results of the per-tile entries above run in
+   that order on each tile. Tile a is the slot range [dense[a] * m_tile, (dense[a] + 1) * m_tile);
+   d_active_dense (device) and h_active_dense (host) hold the same n_active distinct dense tiles, each
+   in [0, m_slots / m_tile). h_cfg (host) = [weight_threshold, forgetting_factor, merge_threshold,
+   eps_psd, eps_lift]; max_primitives < 0 = no cap on the survivors.
+
+   What the per-tile entries decide on the host after a download is decided here per tile on the
+   device: whether the tile takes the max_primitives branch (one segmented descending sort of
+   weight * valid over the active tiles is always launched when max_primitives >= 0), and the
+   merge's no-op tests (fewer than 2 valid slots after the cull). Host-known, and launching nothing:
+   m_tile < 2 or max_pairs <= 0, and the tile-size cap max_tile_size > 0 && m_tile > max_tile_size.
+   Otherwise the merge runs over the tiles in groups of max(1, min(max_sort_keys / P,
+   GC_MAP_MAINTAIN_GROUP_TILES)) with P = m_tile (m_tile - 1) / 2 pair keys per tile, one segmented
+   stable sort per group, and requires m_tile <= 65536. max_sort_keys = 0 selects
+   GC_MAP_MAINTAIN_SORT_KEYS: a group's keys, values and sort buffers take 36 B per key (288 MiB), its
+   per-tile buffers (105 B per slot, 2 KiB of digit counts per tile) at most 40 MiB more; the cull's
+   sort adds 24 B per active slot when max_primitives >= 0 and shares the group's block. A single tile
+   with P > max_sort_keys is sorted whole, as gc_primitive_map_merge_reduce does.
+
+   d_stats (device, caller-allocated, GC_MAP_MAINTAIN_STATS_TILE doubles per active tile): [0] valid
+   count before, [1] n_culled, [2] mass_dropped (0 when nothing was culled), [3] sum of the weights
+   of all slots before the forget, [4] the cull threshold used, [5] n_merged, [6] valid count after,
+   [7] the merge state: GC_MAP_MAINTAIN_MERGE_RAN, _NOOP (m_tile < 2, fewer than 2 valid slots after
+   the cull, or max_pairs <= 0: the reference's exact no-op) or _CAPPED (skipped by the tile-size
+   cap). Nothing is downloaded and the stream is not waited for; the scratch is sized once before
+   the first launch. n_active = 0 succeeds and launches nothing. */
+#define GC_MAP_MAINTAIN_STATS_TILE 8
+#define GC_MAP_MAINTAIN_MERGE_RAN 0
+#define GC_MAP_MAINTAIN_MERGE_NOOP 1
+#define GC_MAP_MAINTAIN_MERGE_CAPPED 2
+#define GC_MAP_MAINTAIN_SORT_KEYS (1 << 23)
+#define GC_MAP_MAINTAIN_GROUP_TILES 4096
+int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, int32_t n_active,
+                                  const int32_t* d_active_dense, const int32_t* h_active_dense,
+                                  const double* h_cfg, int64_t max_primitives, int32_t max_pairs,
+                                  int64_t max_tile_size, int64_t max_sort_keys, double* d_stats);
+
 /* ------------------------------------------------------------------------------------------
  * Map view + OT association (the current PrimitiveMap pose-evidence path).
  * ------------------------------------------------------------------------------------------ */
