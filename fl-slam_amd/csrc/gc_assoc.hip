@@ -334,6 +334,85 @@ __global__ void k_count_u8(int64_t n, const uint8_t* __restrict__ m, unsigned lo
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(out, (unsigned long long)__popcll(b));
 }
 
+// ---- the candidate statistics of the map branch (backend/pipeline.py:879-905)
+// counters: [0] valid rows, [1] Σ distinct tiles over valid rows, [2] Σ valid candidates over valid rows,
+// [3 + c] rows whose count is c - 1: c = 0 the invalid rows (-1.0 in the reference's sort), c = 1 + count else
+constexpr int kCandCounters = 3 + kMaxK + 2;
+
+// One lane per row: its K candidates in registers, valid = view.valid_mask[pool index] (the index clamped
+// into the view, as a JAX gather does), the count of valid ones and of the distinct tile ids among them
+// (:886-895: invalid candidates are tile -1, which counts for nothing). Integer sums, so their order is
+// free: LDS counters per workgroup, then one integer atomic per non-zero counter.
+__global__ void __launch_bounds__(256) k_cand_rows(int64_t N, int K, const uint8_t* __restrict__ valid_meas,
+                                                   const int32_t* __restrict__ pool, const int64_t* __restrict__ tile,
+                                                   const uint8_t* __restrict__ view_valid, int64_t V,
+                                                   unsigned long long* counters) {
+  __shared__ unsigned int cnt[kCandCounters];
+  if ((int)threadIdx.x < kCandCounters) cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) {
+    int64_t t[kMaxK];
+    unsigned int count = 0, distinct = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k) {
+      t[k] = -1;
+      if (k < K) {
+        int64_t p = pool[i * K + k];
+        p = p < 0 ? 0 : (p >= V ? V - 1 : p);
+        if (view_valid[p]) {
+          t[k] = tile[i * K + k];
+          ++count;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k) {
+      bool fresh = t[k] != -1;
+#pragma unroll
+      for (int j = 0; j < k; ++j) fresh = fresh && t[j] != t[k];
+      distinct += fresh ? 1u : 0u;
+    }
+    if (valid_meas[i]) {
+      atomicAdd(&cnt[0], 1u);
+      atomicAdd(&cnt[1], distinct);
+      atomicAdd(&cnt[2], count);
+      atomicAdd(&cnt[3 + 1 + count], 1u);
+    } else {
+      atomicAdd(&cnt[3], 1u);
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < kCandCounters && cnt[threadIdx.x])
+    atomicAdd(&counters[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
+// out3 = [distinct tiles mean, candidates mean, candidates p95]: the means over valid rows divided by
+// max(Σ valid, eps_mass) (:897-900), the p95 the entry idx_p95 of the ascending sort of the counts with -1 at
+// invalid rows (:901-905), read off the histogram. No valid row: zeros (:883-884).
+__global__ void k_cand_finish(const unsigned long long* __restrict__ counters, int K, int64_t idx_p95, double eps_mass,
+                              double* out3) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const unsigned long long nv = counters[0];
+  if (nv == 0) {
+    out3[0] = out3[1] = out3[2] = 0.0;
+    return;
+  }
+  const double denom = fmax((double)nv, eps_mass);
+  out3[0] = (double)counters[1] / denom;
+  out3[1] = (double)counters[2] / denom;
+  unsigned long long below = 0;
+  double p95 = (double)K;
+  for (int c = 0; c <= K + 1; ++c) {
+    below += counters[3 + c];
+    if ((unsigned long long)idx_p95 < below) {
+      p95 = (double)(c - 1);
+      break;
+    }
+  }
+  out3[2] = p95;
+}
+
 }  // namespace
 }  // namespace gc
 
@@ -470,6 +549,37 @@ int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, cons
   GC_HIP(ctx, hipMemcpyAsync(h_cert_out, cert, 12 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (int rc_w = gc::wait_stream(ctx, ctx->stream, "a result download")) return rc_w;
   h_cert_out[12] = (double)hc[1];
+  return GC_OK;
+}
+
+int32_t gc_association_candidate_stats(gc_ctx* ctx, int64_t N, int32_t K, const uint8_t* d_valid_meas,
+                                       const int32_t* d_cand_pool, const int64_t* d_cand_tile,
+                                       const gc_map_view* view, double eps_mass, double* d_out3) {
+  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
+  if (int rc_j = gc::join_side(ctx)) return rc_j;
+  GC_CHECK_ARG(ctx, N >= 0 && N < (int64_t)INT32_MAX, "N must be in [0, 2^31 - 1)");
+  GC_CHECK_ARG(ctx, K >= 1 && K <= kMaxK, "K must be in [1, 16]");
+  GC_CHECK_ARG(ctx, d_out3 != nullptr, "d_out3 is NULL");
+  if (N == 0) {
+    GC_HIP(ctx, hipMemsetAsync(d_out3, 0, 3 * sizeof(double), ctx->stream));
+    return GC_OK;
+  }
+  GC_CHECK_ARG(ctx, view && d_valid_meas && d_cand_pool && d_cand_tile, "NULL argument");
+  const int64_t V = (int64_t)view->n_tiles * view->m_tile_view;
+  GC_CHECK_ARG(ctx, view->n_tiles >= 1 && view->m_tile_view >= 1 && view->valid_mask, "empty view");
+  unsigned long long* counters;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& s) { counters = s.take<unsigned long long>(kCandCounters); }))
+    return rc;
+  GC_HIP(ctx, hipMemsetAsync(counters, 0, kCandCounters * sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_cand_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, N, (int)K, d_valid_meas,
+                     d_cand_pool, d_cand_tile, (const uint8_t*)view->valid_mask, V, counters);
+  GC_LAUNCH_CHECK(ctx);
+  // pipeline.py:903-904: idx = min(int(0.95 * float(N)), N - 1)
+  int64_t idx = (int64_t)(0.95 * (double)N);
+  if (idx > N - 1) idx = N - 1;
+  hipLaunchKernelGGL(k_cand_finish, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)counters, (int)K, idx,
+                     eps_mass, d_out3);
+  GC_LAUNCH_CHECK(ctx);
   return GC_OK;
 }
 

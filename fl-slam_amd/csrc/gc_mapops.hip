@@ -76,9 +76,9 @@ GC_DEV double recency_decay(int64_t seq, int64_t last, double lam) {
   return exp(-lam * (double)dt);
 }
 
-// part: [n_valid, Σ(1 - decay), Σ(1/decay - 1)] over valid slots
-__global__ void __launch_bounds__(256) k_recency(Tile T, int64_t seq, double lam, double min_scale, double* part) {
-  double acc[3] = {0.0, 0.0, 0.0};
+// the thread's slots of the tile (block blockIdx.x of gridDim.x, in slot order): Λ, θ *= decay, and its
+// terms of [n_valid, Σ(1 - decay), Σ(1/decay - 1)] over valid slots
+GC_DEV void recency_slots(const Tile& T, int64_t seq, double lam, double min_scale, double (&acc)[3]) {
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x) {
     const int64_t g = T.s0 + s;
     const bool valid = mValid(T.m, g) != 0;
@@ -95,6 +95,12 @@ __global__ void __launch_bounds__(256) k_recency(Tile T, int64_t seq, double lam
       acc[2] += 1.0 / decay - 1.0;
     }
   }
+}
+
+// part: [n_valid, Σ(1 - decay), Σ(1/decay - 1)] over valid slots
+__global__ void __launch_bounds__(256) k_recency(Tile T, int64_t seq, double lam, double min_scale, double* part) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  recency_slots(T, seq, lam, min_scale, acc);
   block_partials<3>(acc, part);
 }
 
@@ -387,6 +393,14 @@ __global__ void __launch_bounds__(256) k_mm_cull(Tiles S, double thr0, const dou
   block_partials<4>(acc, part + (size_t)blockIdx.y * gridDim.x * 4);
 }
 
+// k_recency with the tile in blockIdx.y (gc_primitive_map_recency_inflate_tiles): the same slots per thread and
+// the same block tree, partials of tile a at part + a * gridDim.x * 3
+__global__ void __launch_bounds__(256) k_mm_recency(Tiles S, int64_t seq, double lam, double min_scale, double* part) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  recency_slots(tile_of(S, blockIdx.y), seq, lam, min_scale, acc);
+  block_partials<3>(acc, part + (size_t)blockIdx.y * gridDim.x * 3);
+}
+
 // k_sum_parts per tile (blockIdx.x): out[a * NV + v]
 template <int NV>
 __global__ void k_mm_sum_parts(const double* __restrict__ part, int blocks, double* out) {
@@ -501,27 +515,6 @@ unsigned part_blocks(int64_t n) {
   return (unsigned)(b < kPartBlocks ? (b > 0 ? b : 1) : kPartBlocks);
 }
 
-int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid) {
-  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
-  if (int rc_j = gc::join_side(ctx)) return rc_j;  // a pipeline's in-scan update may still write the map
-  GC_CHECK_ARG(ctx, map != nullptr, "NULL map");
-  GC_CHECK_ARG(ctx, map->m_slots > 0 && slot0 >= 0 && n_slots >= 0 && slot0 + n_slots <= map->m_slots,
-               "tile range outside the map");
-  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobesOps, "n_lobes must be in [1, 8]");
-  {
-    const char* lay_ = gc::map_layout_error(*map);
-    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
-  }
-  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
-                        map->last_supported_scan_seq && map->last_update_scan_seq,
-               "NULL map field");
-  GC_CHECK_ARG(ctx, !need_valid || map->valid_mask, "valid_mask is required");
-  const bool color = map->cam_mass != nullptr;
-  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
-               "colour fields must be all set or all NULL");
-  return GC_OK;
-}
-
 // reduction pass: launch KER over the tile into part, then fixed-order finish into out (device)
 template <int NV, typename Launch>
 int reduce_into(gc_ctx* ctx, int64_t n, double* part, double* out, Launch launch) {
@@ -557,7 +550,49 @@ InsertScratch insert_layout(Carver& c, int64_t n_slots) {
   return s;
 }
 
+// the checks of a pass over a list of tiles (gc_primitive_map_maintain, gc_primitive_map_recency_inflate_tiles),
+// after check_tile: m_tile divides the map, the host list holds n_active distinct dense tiles of the map
+int check_active_tiles(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, int32_t n_active,
+                       const int32_t* d_active_dense, const int32_t* h_active_dense) {
+  GC_CHECK_ARG(ctx, m_tile > 0 && map->m_slots % m_tile == 0, "m_tile must be > 0 and divide the map's slots");
+  GC_CHECK_ARG(ctx, n_active >= 0 && n_active <= 65535, "n_active must be in [0, 65535]");
+  if (n_active == 0) return GC_OK;
+  GC_CHECK_ARG(ctx, d_active_dense && h_active_dense, "NULL argument");
+  const int64_t n_tiles = map->m_slots / m_tile;
+  GC_CHECK_ARG(ctx, n_active <= n_tiles, "more active tiles than the map holds");
+  std::vector<uint8_t> seen((size_t)n_tiles, 0);
+  for (int a = 0; a < n_active; ++a) {
+    const int64_t d = h_active_dense[a];
+    GC_CHECK_ARG(ctx, d >= 0 && d < n_tiles, "active dense tile outside the map");
+    GC_CHECK_ARG(ctx, !seen[(size_t)d], "duplicate active tile");
+    seen[(size_t)d] = 1;
+  }
+  return GC_OK;
+}
+
 }  // namespace
+
+int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid) {
+  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
+  if (int rc_j = gc::join_side(ctx)) return rc_j;  // a pipeline's in-scan update may still write the map
+  GC_CHECK_ARG(ctx, map != nullptr, "NULL map");
+  GC_CHECK_ARG(ctx, map->m_slots > 0 && slot0 >= 0 && n_slots >= 0 && slot0 + n_slots <= map->m_slots,
+               "tile range outside the map");
+  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobesOps, "n_lobes must be in [1, 8]");
+  {
+    const char* lay_ = gc::map_layout_error(*map);
+    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
+  }
+  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
+                        map->last_supported_scan_seq && map->last_update_scan_seq,
+               "NULL map field");
+  GC_CHECK_ARG(ctx, !need_valid || map->valid_mask, "valid_mask is required");
+  const bool color = map->cam_mass != nullptr;
+  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
+               "colour fields must be all set or all NULL");
+  return GC_OK;
+}
+
 size_t insert_scratch_bytes(int64_t n_slots) {
   Carver c;
   insert_layout(c, n_slots);
@@ -626,6 +661,27 @@ int32_t gc_primitive_map_recency_inflate(gc_ctx* ctx, const gc_primitive_map* ma
       }))
     return rc;
   return h_stats3 ? download(ctx, h_stats3, out, 3 * sizeof(double)) : GC_OK;
+}
+
+int32_t gc_primitive_map_recency_inflate_tiles(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile,
+                                               int32_t n_active, const int32_t* d_active_dense,
+                                               const int32_t* h_active_dense, int64_t scan_seq, double decay_lambda,
+                                               double min_scale, double* d_stats) {
+  if (int rc = check_tile(ctx, map, 0, 0, true)) return rc;  // joins the side stream first
+  if (int rc = check_active_tiles(ctx, map, m_tile, n_active, d_active_dense, h_active_dense)) return rc;
+  if (n_active == 0) return GC_OK;
+  GC_CHECK_ARG(ctx, d_stats != nullptr, "d_stats is NULL");
+  const unsigned nb = part_blocks(m_tile);  // the per-tile entry's partition of a tile of m_tile slots
+  double* part;
+  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) { part = c.take<double>(3 * (size_t)nb * n_active); }))
+    return rc;
+  hipLaunchKernelGGL(k_mm_recency, dim3(nb, (unsigned)n_active), dim3(256), 0, ctx->stream,
+                     Tiles{*map, m_tile, d_active_dense}, scan_seq, decay_lambda, min_scale, part);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_mm_sum_parts<3>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
+                     (int)nb, d_stats);
+  GC_LAUNCH_CHECK(ctx);
+  return GC_OK;
 }
 
 int32_t gc_test_radix_sort(gc_ctx* ctx, const double* d_keys_in, const uint32_t* d_vals_in, int64_t n_seg, int64_t L,
@@ -789,22 +845,10 @@ int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int6
                                   int64_t max_primitives, int32_t max_pairs, int64_t max_tile_size,
                                   int64_t max_sort_keys, double* d_stats) {
   if (int rc = check_tile(ctx, map, 0, 0, true)) return rc;  // joins the side stream first
-  GC_CHECK_ARG(ctx, m_tile > 0 && map->m_slots % m_tile == 0, "m_tile must be > 0 and divide the map's slots");
-  GC_CHECK_ARG(ctx, n_active >= 0 && n_active <= 65535, "n_active must be in [0, 65535]");
+  if (int rc = check_active_tiles(ctx, map, m_tile, n_active, d_active_dense, h_active_dense)) return rc;
   if (n_active == 0) return GC_OK;
-  GC_CHECK_ARG(ctx, d_active_dense && h_active_dense && h_cfg && d_stats, "NULL argument");
+  GC_CHECK_ARG(ctx, h_cfg && d_stats, "NULL argument");
   GC_CHECK_ARG(ctx, max_sort_keys >= 0, "max_sort_keys must be >= 0");
-  const int64_t n_tiles = map->m_slots / m_tile;
-  GC_CHECK_ARG(ctx, n_active <= n_tiles, "more active tiles than the map holds");
-  {
-    std::vector<uint8_t> seen((size_t)n_tiles, 0);
-    for (int a = 0; a < n_active; ++a) {
-      const int64_t d = h_active_dense[a];
-      GC_CHECK_ARG(ctx, d >= 0 && d < n_tiles, "active dense tile outside the map");
-      GC_CHECK_ARG(ctx, !seen[(size_t)d], "duplicate active tile");
-      seen[(size_t)d] = 1;
-    }
-  }
   const double thr0 = h_cfg[0], gamma = h_cfg[1], merge_thr = h_cfg[2], eps_psd = h_cfg[3], eps_lift = h_cfg[4];
   const bool top = max_primitives >= 0;
   const int64_t slots = (int64_t)n_active * m_tile;

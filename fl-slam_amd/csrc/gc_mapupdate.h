@@ -13,6 +13,10 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
                 double eps_lift, double eps_mass, double timestamp, int64_t scan_seq, void* scr,
                 uint32_t** d_counts, unsigned* n_counts);
 
+// The argument check every per-tile entry starts with (gc_mapops.hip; also gc_maptiles.hip): joins the
+// context's side stream, then the tile range, the lobe count, the layout and the field pointers.
+int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid);
+
 size_t insert_scratch_bytes(int64_t n_slots);
 int insert_launch(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots,
                   const gc_insert_batch* batch, double timestamp, int64_t scan_seq, double recency_decay_lambda,

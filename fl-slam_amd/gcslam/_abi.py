@@ -140,6 +140,11 @@ SIGNATURES = {
     "gc_primitive_map_merge_reduce": [_vp, _vp, _i64, _i64, _f64, _i32, _f64, _f64, _vp],
     "gc_primitive_map_update": [_vp, _vp, _vp, _vp, _vp, _f64, _i64, _i64, _vp],
     "gc_primitive_map_maintain": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp],
+    "gc_primitive_map_recency_inflate_tiles": [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _f64, _f64, _vp],
+    "gc_primitive_map_tile_export": [_vp, _vp, _i64, _i64, _vp],
+    "gc_primitive_map_tile_import": [_vp, _vp, _i64, _i64, _vp],
+    "gc_primitive_map_tile_reset": [_vp, _vp, _i64, _i64],
+    "gc_association_candidate_stats": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f64, _vp],
     "gc_extract_map_view": [_vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp],
     "gc_associate_primitives_ot": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp],

@@ -226,6 +226,43 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
                                       realized=float(total_cost)))
 
 
+CANDIDATE_STATS = ("candidate_tiles_per_meas_mean", "candidate_primitives_per_meas_mean",
+                   "candidate_primitives_per_meas_p95")
+
+
+def _candidate_stats_launch(association_result, measurement_batch, map_view: DeviceMapView, eps_mass: float, d_out3):
+    """gc_association_candidate_stats into d_out3 (device, 3 doubles): no download, no wait. The
+    association's and the batch's `.device` arrays are read in place when present."""
+    ctx = map_view.ctx
+    adev = getattr(association_result, "device", None)
+    pool = adev["candidate_pool_indices"] if adev is not None else association_result.candidate_pool_indices
+    tile = adev["candidate_tile_ids"] if adev is not None else association_result.candidate_tile_ids
+    shape = tuple(pool.shape)
+    if len(shape) != 2 or tuple(tile.shape) != shape:
+        raise ValueError(f"candidate_pool_indices {shape} and candidate_tile_ids {tuple(tile.shape)} must be one (N, K)")
+    N, K = shape
+    mdev = getattr(measurement_batch, "device", None)
+    valid = mdev["valid_mask"] if mdev is not None else measurement_batch.valid_mask
+    if not isinstance(valid, _abi.DeviceArray):
+        valid = np.ascontiguousarray(valid).reshape(-1).astype(np.uint8)
+    if int(np.prod(valid.shape)) != N:
+        raise ValueError(f"measurement batch of {tuple(valid.shape)} rows, association of {N}")
+    d_valid, d_pool, d_tile = _abi.upload_many(ctx, [valid, pool, tile], [np.uint8, np.int32, np.int64])
+    _abi.call("gc_association_candidate_stats", ctx.handle, N, K, d_valid.ptr, d_pool.ptr, d_tile.ptr,
+              C.byref(map_view.struct), float(eps_mass), d_out3.ptr, ctx=ctx)
+
+
+def association_candidate_stats(association_result, measurement_batch, map_view: DeviceMapView,
+                                eps_mass: float = GC_EPS_MASS) -> Dict[str, float]:
+    """The candidate statistics the map branch hands to the MapUpdateCert (backend/pipeline.py:879-905):
+    over the valid measurement rows, the mean number of distinct candidate tiles and of valid candidates
+    (cand_valid = map_view.valid_mask[candidate_pool_indices]) and the p95 of the latter, computed on the
+    device (gc_association_candidate_stats) and read with one download. All zero with no valid row."""
+    d_out = _abi.DeviceArray(map_view.ctx, 3, np.float64)
+    _candidate_stats_launch(association_result, measurement_batch, map_view, eps_mass, d_out)
+    return dict(zip(CANDIDATE_STATS, (float(v) for v in d_out.download())))
+
+
 def block_associations_for_fuse(result: PrimitiveAssociationResult, valid_mask,
                                 block_size: int = GC_ASSOC_BLOCK_SIZE):
     """primitive_association.py:561-588 (index bookkeeping on the host result)."""

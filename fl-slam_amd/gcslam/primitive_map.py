@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -49,13 +49,72 @@ class _FuseStruct(C.Structure):
         "sources")]
 
 
+class TileMove(NamedTuple):
+    """One slab of a residency plan: the key that leaves it, the key that comes in, and whether that key
+    is loaded from the host store (else it is created empty)."""
+    slab: int
+    evicted: int
+    incoming: int
+    load: bool
+
+
+def plan_tile_residency(resident_keys: Sequence[int], last_used: Sequence[int], wanted_keys: Sequence[int],
+                        stored_keys: Iterable[int]) -> List[TileMove]:
+    """Which slabs change so that every wanted key is resident (host only, no device). Wanted keys that
+    are resident stay where they are. Victims are the slabs whose key is not wanted, least recently
+    wanted first (last_used[slab]: the stamp of the last call that wanted the slab's key), ties by the
+    lowest slab. Incoming keys take the victims in the order of wanted_keys; a key in stored_keys is
+    loaded, any other is created empty. ValueError for duplicate keys or more wanted keys than slabs."""
+    resident = [int(k) for k in resident_keys]
+    wanted = [int(k) for k in wanted_keys]
+    stored = {int(k) for k in stored_keys}
+    if len(last_used) != len(resident):
+        raise ValueError(f"{len(last_used)} use stamps for {len(resident)} slabs")
+    if len(set(wanted)) != len(wanted):
+        raise ValueError(f"duplicate tile keys in {wanted}")
+    if len(set(resident)) != len(resident):
+        raise ValueError(f"duplicate resident tile keys in {resident}")
+    if len(wanted) > len(resident):
+        raise ValueError(f"{len(wanted)} tiles wanted, the map holds {len(resident)} slabs")
+    want = set(wanted)
+    here = set(resident)
+    victims = sorted((d for d, k in enumerate(resident) if k not in want), key=lambda d: (int(last_used[d]), d))
+    incoming = [k for k in wanted if k not in here]
+    return [TileMove(d, resident[d], k, k in stored) for d, k in zip(victims, incoming)]
+
+
+@dataclass
+class TileResidency:
+    """What DevicePrimitiveMap.ensure_tiles did: the keys found resident, loaded from the host store,
+    created empty and evicted to the store, and the dense tile of every requested key, in request order."""
+    hits: List[int]
+    loaded: List[int]
+    created: List[int]
+    evicted: List[int]
+    dense: List[int]
+
+
+@dataclass
+class _StoredTile:
+    """A tile that is not resident: its image (gc_primitive_map_tile_export), its count in the AtlasMap
+    bookkeeping (None: never recorded) and whether its colours were the fuse's estimate."""
+    image: np.ndarray
+    tile_count: Optional[int]
+    colors_current: bool
+
+
 class DevicePrimitiveMap:
     """n_tiles x m_tile slots of PrimitiveMapTile fields (create_empty_tile, primitive_map.py:148-175).
 
     packed=True (default) keeps one record per slot in HBM (gc_primitive_map_record_layout: the
     fuse's read-modify-write fields in the record's first two 128-B lines); upload / download
     transpose to and from the reference's per-field arrays on the device (gc_copy_strided).
-    packed=False keeps the per-field arrays themselves."""
+    packed=False keeps the per-field arrays themselves.
+
+    The n_tiles slabs hold the tiles named by tile_keys. ensure_tiles brings other keys in, as the
+    reference's AtlasMap creates tiles on demand (primitive_map.py:183-211): the tile that has to leave
+    a slab goes to a host store owned by the map (its image, tile_count and colour flag) and comes back
+    from there when it is wanted again. next_global_id and total_count cover resident and stored tiles."""
 
     def __init__(self, n_tiles: int, m_tile: int, n_lobes: int = GC_VMF_N_LOBES, track_colors: bool = True,
                  ctx=None, packed: bool = True):
@@ -73,10 +132,12 @@ class DevicePrimitiveMap:
         self.packed = bool(packed)
         self.ptrs: Dict[str, int] = {}
         self.fields: Dict[str, _abi.DeviceArray] = {}  # per-field arrays (packed=False)
+        off = np.zeros(16, np.int64)
+        sb = C.c_int64(0)
+        _abi.call("gc_primitive_map_record_layout", self.n_lobes, off.ctypes.data, C.byref(sb))
+        self.image_slot_bytes = int(sb.value)  # one slot of a tile image, whatever the map's layout
+        self._image_off = off.copy()
         if self.packed:
-            off = np.zeros(16, np.int64)
-            sb = C.c_int64(0)
-            _abi.call("gc_primitive_map_record_layout", self.n_lobes, off.ctypes.data, C.byref(sb))
             self.slot_bytes = int(sb.value)
             self.records = _abi.DeviceArray(self.ctx, M * self.slot_bytes, np.uint8)
             self.records.zero()
@@ -106,6 +167,11 @@ class DevicePrimitiveMap:
         self.tile_count: Dict[int, int] = {}
         # tile keys of the dense tiles (the reference's packed MA-hex tile ids); default 0..n-1
         self.tile_keys: List[int] = list(range(self.n_tiles))
+        # tile residency (ensure_tiles): the tiles that are not resident, by key, and per slab the stamp
+        # of the last ensure_tiles call that wanted its key
+        self._store: Dict[int, _StoredTile] = {}
+        self._last_used: List[int] = [0] * self.n_tiles
+        self._use_clock = 0
 
     @property
     def colors_current(self) -> bool:
@@ -156,7 +222,96 @@ class DevicePrimitiveMap:
         keys = [int(k) for k in keys]
         if len(keys) != self.n_tiles or len(set(keys)) != len(keys):
             raise ValueError("tile keys must be n_tiles distinct ids")
+        if any(k in self._store for k in keys):
+            raise ValueError("a tile key of the host store cannot name a slab: ensure_tiles loads it")
         self.tile_keys = keys
+
+    # ------------------------------------------------------------------------- tile residency
+    def stored_keys(self) -> List[int]:
+        """The keys of the tiles held by the host store (not resident)."""
+        return list(self._store)
+
+    def _attached(self) -> bool:
+        for ref in self._listeners:
+            pipe = ref()
+            if pipe is not None and getattr(pipe, "_smap", None) is self:
+                return True
+        return False
+
+    def ensure_tiles(self, keys) -> TileResidency:
+        """Make every tile key of `keys` resident (plan_tile_residency): every victim is exported to the
+        host store (always: upload() does not maintain tile_count, so the host cannot know a slab is
+        empty), every incoming slab is imported from the store or reset to the empty tile, then
+        tile_keys, tile_count, the colour flags and the store follow, and the stream is waited for once.
+        When every key is resident nothing is launched and nothing is waited for. RuntimeError while a
+        BatchedScanPipeline has the map attached: its in-scan update addresses flat slots."""
+        keys = [int(k) for k in keys]
+        if self._attached():
+            raise RuntimeError("ensure_tiles while a pipeline has the map attached: detach it first "
+                               "(attach_primitive_map(None))")
+        plan = plan_tile_residency(self.tile_keys, self._last_used, keys, self._store.keys())
+        hits = [k for k in keys if k in self.tile_keys]
+        if plan:
+            m, st = self.m_tile, self.struct()
+            images = [np.empty(m * self.image_slot_bytes, np.uint8) for _ in plan]
+            for mv, img in zip(plan, images):  # 1. every victim out
+                _abi.call("gc_primitive_map_tile_export", self.ctx.handle, C.byref(st), mv.slab * m, m,
+                          img.ctypes.data, ctx=self.ctx)
+            for mv in plan:                    # 2. every incoming slab
+                if mv.load:
+                    _abi.call("gc_primitive_map_tile_import", self.ctx.handle, C.byref(st), mv.slab * m, m,
+                              self._store[mv.incoming].image.ctypes.data, ctx=self.ctx)
+                else:
+                    _abi.call("gc_primitive_map_tile_reset", self.ctx.handle, C.byref(st), mv.slab * m, m,
+                              ctx=self.ctx)
+            loaded = []                        # 3. the bookkeeping; the loaded images live until the wait
+            for mv, img in zip(plan, images):
+                self._store[mv.evicted] = _StoredTile(img, self.tile_count.pop(mv.slab, None),
+                                                      bool(self._tile_cc[mv.slab]))
+            for mv in plan:
+                self.tile_keys[mv.slab] = mv.incoming
+                self._tile_cc[mv.slab] = False  # an empty tile: rgb gray, colors 0, as a new map
+                if mv.load:
+                    t = self._store.pop(mv.incoming)
+                    loaded.append(t)
+                    if t.tile_count is not None:
+                        self.tile_count[mv.slab] = t.tile_count
+                    self._tile_cc[mv.slab] = t.colors_current
+            self.ctx.sync()                    # 4. the one wait
+            del loaded
+        self._use_clock += 1
+        dense = [self.tile_keys.index(k) for k in keys]
+        for d in dense:
+            self._last_used[d] = self._use_clock
+        return TileResidency(hits=hits, loaded=[mv.incoming for mv in plan if mv.load],
+                             created=[mv.incoming for mv in plan if not mv.load],
+                             evicted=[mv.evicted for mv in plan], dense=dense)
+
+    def image_fields(self, image) -> Dict[str, np.ndarray]:
+        """The fields this map holds out of a tile image (gc_primitive_map_tile_export), as download_tile
+        returns them."""
+        rec = np.asarray(image, np.uint8).reshape(-1, self.image_slot_bytes)
+        order = _F64 + _I64 + _COL + _MAINT
+        out = {}
+        for k in self.ptrs:
+            o, rb = int(self._image_off[order.index(k)]), self._row_bytes(k)
+            out[k] = np.ascontiguousarray(rec[:, o:o + rb]).view(self.dtypes[k]).reshape(
+                (rec.shape[0],) + self.shapes[k][1:])
+        return out
+
+    def key_fields(self, key: int) -> Dict[str, np.ndarray]:
+        """The fields of the tile with key `key`, resident (a download) or in the host store."""
+        d = self.dense_tile(key)
+        if d >= 0:
+            return self.download_tile(d)
+        if int(key) not in self._store:
+            raise KeyError(f"tile {key} is neither resident nor stored")
+        return self.image_fields(self._store[int(key)].image)
+
+    def key_count(self, key: int) -> Optional[int]:
+        """tile_count of the tile with key `key`, resident or stored (None: never recorded)."""
+        d = self.dense_tile(key)
+        return self.tile_count.get(d) if d >= 0 else self._store[int(key)].tile_count
 
     def dense_tile(self, key: int) -> int:
         """Dense tile index holding tile key `key`, or -1 (an empty tile for the view)."""
@@ -324,6 +479,7 @@ class PrimitiveMapRecencyInflateStats:
     staleness_inflation_strength: float
     staleness_cov_inflation_trace: float
     stale_precision_downscale_total: float
+    per_tile: Optional[np.ndarray] = None  # (n, 3), the batched operator only: each visited tile's sums
 
 
 def primitive_map_recency_inflate(atlas_map: DevicePrimitiveMap, tile_ids: List[int], scan_seq: int,
@@ -346,6 +502,69 @@ def primitive_map_recency_inflate(atlas_map: DevicePrimitiveMap, tile_ids: List[
     return (atlas_map, CertBundle.create_exact(chart_id=chart_id, anchor_id=anchor_id),
             ExpectedEffect(objective_name="primitive_map_recency_inflate", predicted=float(n_valid),
                            realized=float(n_valid)), stats)
+
+
+def _recency_tiles_dense(atlas_map: DevicePrimitiveMap, tile_keys) -> List[int]:
+    """The dense tiles of the keys the batched inflate visits: a key the map does not know is skipped
+    (primitive_map.py:1420-1424), a key of the host store is an error."""
+    dense = []
+    for k in tile_keys:
+        d = atlas_map.dense_tile(int(k))
+        if d < 0:
+            if int(k) in atlas_map._store:
+                raise ValueError(f"tile {int(k)} is in the host store, not resident: ensure_tiles first")
+            continue
+        dense.append(d)
+    if len(set(dense)) != len(dense):
+        raise ValueError(f"duplicate tile keys in {[int(k) for k in tile_keys]}")
+    if dense and "valid_mask" not in atlas_map.ptrs:
+        raise ValueError("the map has no maintenance fields")
+    return dense
+
+
+def _recency_tiles_launch(atlas_map: DevicePrimitiveMap, d_dense, h_dense: np.ndarray, scan_seq: int,
+                          recency_decay_lambda: float, min_scale: float, d_stats) -> None:
+    """gc_primitive_map_recency_inflate_tiles on the map's stream: no download, no wait."""
+    _abi.call("gc_primitive_map_recency_inflate_tiles", atlas_map.ctx.handle, C.byref(atlas_map.struct()),
+              atlas_map.m_tile, int(h_dense.shape[0]), d_dense.ptr, h_dense.ctypes.data, int(scan_seq),
+              float(recency_decay_lambda), float(min_scale), d_stats.ptr, ctx=atlas_map.ctx)
+
+
+def _recency_tiles_finish(atlas_map, per_tile: np.ndarray, chart_id: str, anchor_id: str):
+    """The operator's return from the per-tile statistics (n, 3), added in tile order as the reference's
+    loop adds them (primitive_map.py:1425-1470)."""
+    st = np.asarray(per_tile, np.float64).reshape(-1, 3)
+    n_valid = downscale = trace = 0.0
+    for row in st:
+        n_valid += row[0]
+        downscale += row[1]
+        trace += row[2]
+    stats = PrimitiveMapRecencyInflateStats(staleness_inflation_strength=float(downscale / max(n_valid, 1.0)),
+                                            staleness_cov_inflation_trace=float(trace),
+                                            stale_precision_downscale_total=float(downscale), per_tile=st.copy())
+    return (atlas_map, CertBundle.create_exact(chart_id=chart_id, anchor_id=anchor_id),
+            ExpectedEffect(objective_name="primitive_map_recency_inflate", predicted=float(n_valid),
+                           realized=float(n_valid)), stats)
+
+
+def primitive_map_recency_inflate_tiles(atlas_map: DevicePrimitiveMap, tile_keys, scan_seq: int,
+                                        recency_decay_lambda: float = GC_RECENCY_DECAY_LAMBDA,
+                                        min_scale: float = GC_RECENCY_MIN_SCALE, chart_id: str = GC_CHART_ID,
+                                        anchor_id: str = "primitive_map_recency_inflate"):
+    """primitive_map_recency_inflate (primitive_map.py:1400-1490) over the tiles with keys `tile_keys` in
+    one device pass (gc_primitive_map_recency_inflate_tiles) and one download -> (atlas_map, cert,
+    effect, stats), with the map and the bits of the per-tile operator looped over the same tiles;
+    stats.per_tile holds [n_valid, Σ(1 - decay), Σ(1/decay - 1)] of each visited tile. A key the map does
+    not know is skipped, as the reference skips a missing tile; a key that is in the host store but not
+    resident raises ValueError."""
+    dense = _recency_tiles_dense(atlas_map, tile_keys)
+    if not dense:
+        return _recency_tiles_finish(atlas_map, np.zeros((0, 3)), chart_id, anchor_id)
+    h_dense = np.asarray(dense, np.int32)
+    d_dense, = _abi.upload_many(atlas_map.ctx, [h_dense], [np.int32])
+    d_stats = _abi.DeviceArray(atlas_map.ctx, (len(dense), 3), np.float64)
+    _recency_tiles_launch(atlas_map, d_dense, h_dense, scan_seq, recency_decay_lambda, min_scale, d_stats)
+    return _recency_tiles_finish(atlas_map, d_stats.download(), chart_id, anchor_id)  # the one download
 
 
 @dataclass

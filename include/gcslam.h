@@ -893,6 +893,46 @@ int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int6
                                   const double* h_cfg, int64_t max_primitives, int32_t max_pairs,
                                   int64_t max_tile_size, int64_t max_sort_keys, double* d_stats);
 
+/* primitive_map_recency_inflate (primitive_map.py:1400-1490) over a list of tiles in one pass: what
+   gc_primitive_map_recency_inflate does to each tile [dense[a] * m_tile, (dense[a] + 1) * m_tile), with
+   no download and no wait. The tile list and its checks are those of gc_primitive_map_maintain
+   (d_active_dense on the device and h_active_dense on the host hold the same n_active distinct dense
+   tiles, each in [0, m_slots / m_tile)). d_stats (device, caller-allocated, 3 doubles per tile in tile
+   order) = [n_valid, sum (1 - decay), sum (1/decay - 1)] over the tile's valid slots, bit for bit what
+   the per-tile entry returns for that tile: the same slots per thread, the same block partition and
+   the same fixed-order tree, no float atomics. n_active = 0 succeeds and launches nothing. */
+int32_t gc_primitive_map_recency_inflate_tiles(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile,
+                                               int32_t n_active, const int32_t* d_active_dense,
+                                               const int32_t* h_active_dense, int64_t scan_seq,
+                                               double decay_lambda, double min_scale, double* d_stats);
+
+/* ------------------------------------------------------------------------------------------
+ * Tile residency: the reference's AtlasMap creates tiles on demand (primitive_map.py:183-211); the
+ * device map holds a fixed number of slabs, and a tile that has to leave its slab is kept by the
+ * host as an image. Each entry works on one tile [slot0, slot0 + n_slots), as the maintenance
+ * entries do.
+ *
+ * The image of a tile is n_slots records of gc_primitive_map_record_layout(n_lobes) (n_slots x
+ * slot_bytes_out bytes), whatever the map's own layout, so an image exported from a packed map can
+ * be imported into a per-field map and back. valid_mask is the low byte of its 8-byte word; padding
+ * bytes of an image are not part of its contract. A packed map holding all sixteen fields moves the
+ * image with one copy; any other map gathers / scatters it through the context's scratch with one
+ * kernel. Fields the map does not hold (no colour tracking, no maintenance fields) are written as
+ * create_empty_tile has them (primitive_map.py:148-175: zeros, rgb = 0.5) on export and ignored on
+ * import.
+ *
+ * NONE OF THESE ENTRIES WAITS FOR THE STREAM. The caller waits once (gc_ctx_synchronize) after the
+ * last entry of its plan, and h_image must stay allocated, and for an import unchanged, until then.
+ * ------------------------------------------------------------------------------------------ */
+int32_t gc_primitive_map_tile_export(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots,
+                                     void* h_image);
+int32_t gc_primitive_map_tile_import(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots,
+                                     const void* h_image);
+/* Every slot of the tile becomes create_empty_tile's (primitive_map.py:148-175): zeros in every field
+   the map holds, rgb = 0.5. One kernel. The caller marks the tile's colours not current
+   (gc_primitive_map.colors_current), as for a new map. */
+int32_t gc_primitive_map_tile_reset(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots);
+
 /* ------------------------------------------------------------------------------------------
  * Map view + OT association (the current PrimitiveMap pose-evidence path).
  * ------------------------------------------------------------------------------------------ */
@@ -940,6 +980,19 @@ int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, cons
                                    double* d_resp_out, int32_t* d_cand_out, int64_t* d_cand_tile_out,
                                    int64_t* d_cand_slot_out, double* d_row_mass_out, double* d_cost_out,
                                    double* h_cert_out);
+
+/* The candidate statistics of the map branch (backend/pipeline.py:879-905) from an association's pool
+   indices int32 (N, K) and candidate tile ids int64 (N, K), the measurement rows' valid mask (N) and
+   the view the indices point into (clamped into it, as a JAX gather does). Per row: cand_valid =
+   view.valid_mask[pool index], the number of valid candidates, and the number of distinct tile ids
+   among them. d_out3 (device) = [candidate_tiles_per_meas_mean, candidate_primitives_per_meas_mean,
+   candidate_primitives_per_meas_p95]: the two sums over valid rows divided by max(sum valid,
+   eps_mass), and entry min(int(0.95 N), N - 1) of the ascending sort of the counts with -1 at invalid
+   rows, taken from a histogram of the K + 2 possible values. Integer sums: exact and order-free. No
+   valid row (or N = 0): all three are 0. 1 <= K <= 16. Nothing is downloaded, no wait. */
+int32_t gc_association_candidate_stats(gc_ctx* ctx, int64_t N, int32_t K, const uint8_t* d_valid_meas,
+                                       const int32_t* d_cand_pool, const int64_t* d_cand_tile,
+                                       const gc_map_view* view, double eps_mass, double* d_out3);
 
 #define GC_VPE_PARTS 26  /* per hypothesis: L_trans(9) h_trans(3) L_rot(9) h_rot(3) cost_trans cost_rot */
 #define GC_VPE_CERT 4    /* host: [n_valid_meas, n_valid_map, sum_row_masses, mean_row_mass] */
