@@ -10,6 +10,12 @@ namespace gc {
 
 constexpr int NF_BASE = 19;   // [1, d(3), dd(6: 00 01 02 11 12 22), p(3), pp(6)] x w
 constexpr int REC_EXTRA = 4;  // [entropy_sum, max_resp, sum_w, n_points]
+// The lean feature set of the persistent bins form (k_bins_io): [1, d(3), p(3), pp(6)] x w, the base
+// features without the direction scatter dd, in the base order. Only the bin map's increment reads a
+// hypothesis's per-bin scatter (pushforward_bin), and only global hypothesis 0 feeds the map
+// (bin_scatter_full, gc_pipe.h): every other hypothesis's tasks accumulate the lean set. A lean
+// record fills the first B * NF_LEAN + REC_EXTRA doubles of its B * NF_BASE + REC_EXTRA slot.
+constexpr int NF_LEAN = 13;
 // k_evidence's per-bin table (64 x 16 doubles) also receives the folded finalize's summed record
 // (B * NF_BASE + REC_EXTRA doubles): the fold is taken only when the record fits it (B <= 53), larger B
 // keep the split finalize kernel (scan_bins_pipeline), so the sums never run into the table's neighbours
@@ -20,8 +26,10 @@ inline constexpr bool fold_record_fits(int B) { return B * NF_BASE + REC_EXTRA <
 // entries per thread and KU chunks per batch in flight; a ragged last batch loads zeros past the last
 // chunk (+0 and fmax(·, 0) leave every entry, all >= 0 for the max, unchanged): one L2 round trip per
 // batch. Entries past KE x blockDim go one chunk at a time (none at B <= 48 with the base features).
+// RS: doubles between two chunk records, RL <= RS: the entries a record holds (a lean record is
+// shorter than its slot).
 template <int KE, int KU>
-GC_DEV void finalize_reduce(const double* __restrict__ P, int RL, int imax, int64_t chunks, double* sm) {
+GC_DEV void finalize_reduce(const double* __restrict__ P, int RS, int RL, int imax, int64_t chunks, double* sm) {
   const int nt = blockDim.x;
   int ie[KE];
   double v[KE];
@@ -35,7 +43,7 @@ GC_DEV void finalize_reduce(const double* __restrict__ P, int RL, int imax, int6
 #pragma unroll
     for (int e = 0; e < KE; ++e)
 #pragma unroll
-      for (int u = 0; u < KU; ++u) x[e][u] = (ie[e] < RL && c + u < chunks) ? P[(c + u) * RL + ie[e]] : 0.0;
+      for (int u = 0; u < KU; ++u) x[e][u] = (ie[e] < RL && c + u < chunks) ? P[(c + u) * RS + ie[e]] : 0.0;
 #pragma unroll
     for (int e = 0; e < KE; ++e)
 #pragma unroll
@@ -46,22 +54,29 @@ GC_DEV void finalize_reduce(const double* __restrict__ P, int RL, int imax, int6
     if (ie[e] < RL) sm[ie[e]] = v[e];
   for (int i = threadIdx.x + KE * nt; i < RL; i += nt) {
     double w = 0.0;
-    for (int64_t cc = 0; cc < chunks; ++cc) w = i == imax ? fmax(w, P[cc * RL + i]) : w + P[cc * RL + i];
+    for (int64_t cc = 0; cc < chunks; ++cc) w = i == imax ? fmax(w, P[cc * RS + i]) : w + P[cc * RS + i];
     sm[i] = w;
   }
 }
 // One bin's finalize (binning.py:139-209): its NF summed moments a -> the GC_BIN_STATS row o
 // (p̄, Σ_p PSD-projected, κ; N, s_dir, scatter and the raw sums), its projection delta and
-// mass-epsilon ratio.
+// mass-epsilon ratio. NF == NF_LEAN: a holds the lean features (no direction scatter). zero_scatter (implied by
+// the lean layout): o[4:13] is written as 0.0 — a hypothesis whose scatter nothing reads carries zeros there from
+// either record layout, never another scan's values or a value that depends on the kernel instantiation.
 GC_DEV void finalize_bin(const double* a, int NF, double eps_psd, double eps_mass, double* o, double* psd_out,
-                         double* er_out) {
+                         double* er_out, bool zero_scatter = false) {
+  const bool lean = NF == NF_LEAN;
   const double N = a[0];
   const double denom = N + eps_mass + kF64Eps;
   const double invN = 1.0 / denom, er = eps_mass / denom;
   const double sd[3] = {a[1], a[2], a[3]};
-  const double Ssc[9] = {a[4], a[5], a[6], a[5], a[7], a[8], a[6], a[8], a[9]};
-  const double sp[3] = {a[10], a[11], a[12]};
-  const double Spp[9] = {a[13], a[14], a[15], a[14], a[16], a[17], a[15], a[17], a[18]};
+  const double* as = lean ? a : a + 4;   // dd (unread when lean)
+  const double* ap = lean ? a + 4 : a + 10;  // p, pp
+  double Ssc[9] = {as[0], as[1], as[2], as[1], as[3], as[4], as[2], as[4], as[5]};
+  if (lean || zero_scatter)
+    for (int k = 0; k < 9; ++k) Ssc[k] = 0.0;
+  const double sp[3] = {ap[0], ap[1], ap[2]};
+  const double Spp[9] = {ap[3], ap[4], ap[5], ap[4], ap[6], ap[7], ap[5], ap[7], ap[8]};
   double pb[3] = {sp[0] * invN, sp[1] * invN, sp[2] * invN};
   double Sr[9], Sp[9], c6[6];
   for (int i = 0; i < 3; ++i)

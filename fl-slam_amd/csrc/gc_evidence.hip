@@ -95,17 +95,23 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
     // per bin; the split kernel's ticket is published here (the bins have completed)
     if (hl == 0 && t == 0 && S.done_word)
       __hip_atomic_store(S.done_word, S.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const int RL = B * NF_BASE + REC_EXTRA;
+    // a hypothesis whose scatter nothing reads (!bin_scatter_full) gets zeros there; its records are lean
+    // when the bins launch ran the lean set for it (S.lean_records: long tasks): NFh features per bin at the
+    // head of each record slot
+    const bool zero_scatter = !bin_scatter_full(P, hl), lean = zero_scatter && S.lean_records != 0;
+    const int NFh = lean ? NF_LEAN : NF_BASE;
+    const int RS = B * NF_BASE + REC_EXTRA;
     // 11 chunks per batch: the 21-22 chunk records of C5 / H = 256 in two L2 round trips (8: three;
     // the same order and bits, 1.1897 -> 1.1890 ms at H = 256, tools/r4_ab_slots.sh)
-    finalize_reduce<4, 11>(S.fin_part + (int64_t)hl * S.fin_chunks * RL, RL, B * NF_BASE + 1, S.fin_chunks, tab);
+    finalize_reduce<4, 11>(S.fin_part + (int64_t)hl * S.fin_chunks * RS, RS, B * NFh + REC_EXTRA, B * NFh + 1,
+                           S.fin_chunks, tab);
     __syncthreads();
     if (t < B) {
       double* ax = P.binaux + ((int64_t)hl * B + t) * 2;
-      finalize_bin(tab + t * NF_BASE, NF_BASE, P.eps_psd, eps, P.stats + ((int64_t)hl * B + t) * GC_BIN_STATS, ax,
-                   ax + 1);
+      finalize_bin(tab + t * NFh, NFh, P.eps_psd, eps, P.stats + ((int64_t)hl * B + t) * GC_BIN_STATS, ax, ax + 1,
+                   zero_scatter);
     } else if (t == 64) {
-      const double* ex = tab + B * NF_BASE;
+      const double* ex = tab + B * NFh;
       double* c = P.bincert + (int64_t)hl * GC_BIN_CERT;
       c[4] = ex[0] / (ex[3] + eps);
       c[5] = ex[1];

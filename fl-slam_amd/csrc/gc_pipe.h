@@ -39,6 +39,8 @@ struct PipeDev {
   int geom_H;    // bins chunk geometry as for this many hypotheses (0: Hl)
   int predict_route;  // 0: split predict (lift solves, L_pred in the bins launch) when certified; 1: always
                       // the factorised chain in the predict kernel (gc_pipeline_set_predict_route)
+  int bin_scatter_all;  // 0: only global hypothesis 0's bin tasks accumulate the per-bin direction scatter
+                        // (bin_scatter_full); 1: every hypothesis's (gc_pipeline_set_bin_scatter_all)
   int cus;       // compute units of the pipeline's device (ctx->device, queried once at create): every
                  // grid-size decision (predict's budget workgroups, the chain kernels' occupancy) uses it
   int64_t n_in, n_cap;
@@ -91,6 +93,18 @@ struct PipeDev {
                                            // process 7 x 6x6 masked, measurement 3 x 3x3 symmetrised
 };
 
+// Local hypothesis hl's bin tasks take the full feature set (its bin statistics carry the per-bin
+// direction scatter, columns 4:13): global hypothesis 0, whose scatter k_evidence pushes into the bin
+// map's increment, or every hypothesis with the diagnostic switch on. A function of the global index
+// alone, so a hypothesis's statistics do not depend on how the hypotheses are sharded.
+__host__ __device__ inline bool bin_scatter_full(const PipeDev& P, int hl) {
+  return P.bin_scatter_all != 0 || P.h_begin + hl == 0;
+}
+// the local hypotheses with bin_scatter_full: [0, this count) (h_begin >= 0)
+__host__ __device__ inline int bin_scatter_full_count(const PipeDev& P) {
+  return P.bin_scatter_all != 0 ? P.Hl : (P.h_begin == 0 ? 1 : 0);
+}
+
 constexpr int kIwRawLen = 7 * 36 + 3 * 9;
 // scan-level projection certificates after the per-hypothesis ones: the barycenter L, the 7 process-IW
 // blocks, the 3 measurement-IW blocks, Q
@@ -110,6 +124,8 @@ struct ScanArgs {
   // launch's chunk records and count; null when the split finalize kernel ran
   const double* fin_part;
   int64_t fin_chunks;
+  int lean_records;                        // with fin_part: a lean-set hypothesis's records hold the lean set
+                                           // (the late-ticket bins launch); 0: every record is a full one
   int64_t* done_word;                      // with fin_part: the ticket published by k_evidence
   int64_t ticket;
 };
@@ -160,6 +176,7 @@ namespace gc {
 struct BinsFold {
   const double* part = nullptr;
   int64_t chunks = 0;
+  bool lean_records = false;  // the launch's lean-set hypotheses wrote lean records (long tasks)
 };
 int32_t scan_bins_pipeline(gc_ctx* ctx, const PipeDev& P, const ScanArgs& S, const double* d_odom, bool io,
                            const double* d_pts, const double* d_t, const double* d_w, int64_t n_in,

@@ -933,6 +933,7 @@ static int32_t scan_local_impl(gc_pipeline* p, int32_t slot, double scan_start, 
   gc::ScanArgs Se = S;  // the evidence launch's: with the finalize folded in, its records and the ticket
   Se.fin_part = fold.part;
   Se.fin_chunks = fold.chunks;
+  Se.lean_records = fold.lean_records ? 1 : 0;
   Se.done_word = fold.part ? dw : nullptr;
   Se.ticket = p->ticket;
   if (!smap_active(p)) s.consumed_ticket = p->ticket;
@@ -1092,6 +1093,13 @@ int32_t gc_pipeline_set_predict_route(gc_pipeline* p, int32_t route) {
   GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_CHECK_ARG(p->ctx, route == 0 || route == 1, "route must be 0 (split) or 1 (factorised)");
   p->P.predict_route = route;
+  return GC_OK;
+}
+
+int32_t gc_pipeline_set_bin_scatter_all(gc_pipeline* p, int32_t on) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  p->P.bin_scatter_all = on != 0 ? 1 : 0;
   return GC_OK;
 }
 

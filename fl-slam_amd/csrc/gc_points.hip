@@ -887,13 +887,16 @@ GC_DEV int64_t uniform_i64(int64_t v) {
 // epilogue runs before mid() issues the next task's loads (a later wait on scratch or on the staged
 // values would otherwise wait for those loads' HBM round trip as well). One barrier, the 4-wave sum in
 // a fixed order, and the caller's closing barrier.
-template <int BPL, int NX, int DF = -1, bool FULL = false, int WS = 0, typename Pre = NoHook, typename Mid = NoHook>
-GC_DEV void write_partial_record_mfma(const v4d (&acc4)[BPL], double (&accx)[BPL][NX], double ent, double mxr,
+// NC: the MFMA columns the record keeps (columns NC.. of the tiles are dropped; the lean feature set's 13).
+template <int BPL, int NX, int DF = -1, bool FULL = false, int WS = 0, int NC = 16, typename Pre = NoHook,
+          typename Mid = NoHook>
+GC_DEV void write_partial_record_mfma(const v4d (&acc4)[BPL], double (&accx)[BPL][NX > 0 ? NX : 1], double ent, double mxr,
                                       double sumw, double npts, int B_, double* lds, double* rec,
                                       const Pre& pre = Pre(), const Mid& mid = Mid()) {
   const int B = FULL ? 16 * BPL : B_;  // FULL: a compile-time bin count (immediate LDS offsets, no bounds branches)
   constexpr int ND = DF >= 0 ? 1 : 0;
-  constexpr int NF = ND + 16 + NX;
+  constexpr int NF = ND + NC + NX;
+  static_assert(NC == 16 || (DF < 0 && NX == 0), "dropped columns: the lean set, every feature on the matrix core");
   static_assert(WS >= 16 * BPL * NF + 3, "a wave's slab holds its record tiles");
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, bl = lane & 15;
   const int fcol = (DF >= 0 && bl >= DF) ? bl + 1 : bl;  // the feature of MFMA column bl
@@ -915,12 +918,12 @@ GC_DEV void write_partial_record_mfma(const v4d (&acc4)[BPL], double (&accx)[BPL
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int b = 16 * j + g + 4 * r;
-      if (b < B) W[b * NF + fcol] = acc4[j][r];
+      if (b < B && (NC == 16 || bl < NC)) W[b * NF + fcol] = acc4[j][r];
     }
     const int b = 16 * j + bl;
     if (g == 0 && b < B)
 #pragma unroll
-      for (int t = 0; t < NX; ++t) W[b * NF + ND + 16 + t] = accx[j][t];
+      for (int t = 0; t < NX; ++t) W[b * NF + ND + NC + t] = accx[j][t];
   }
   if (lane == 0) {
     W[B * NF + 0] = e;
@@ -1075,6 +1078,21 @@ GC_DEV void task_operands(const FusedArgs& A, int h, int64_t c, int64_t n_sel, i
   ta.ok = ok;
   ta.valid = true;
 }
+// The persistent form's ticket order: tickets [0, Tf) are the tasks of the launch's nf full-set
+// hypotheses (local 0 .. nf - 1), the rest those of its nl lean-set ones (local nf .. nf + nl - 1), each
+// range chunk-major (the workgroups in flight share a chunk's raw points across hypotheses in L2).
+// Every puller runs its full-set tasks in one loop and its lean-set tasks in the next (k_bins_io), so
+// the two variants never meet inside one loop.
+struct TaskOrder {
+  unsigned Tf;
+  int nf, nl;
+};
+GC_DEV void task_of(const TaskOrder& O, unsigned t, int* h, int64_t* c) {
+  const bool f = t < O.Tf;
+  const unsigned u = f ? t : t - O.Tf, n = (unsigned)(f ? O.nf : O.nl);
+  *c = (int64_t)(u / n);
+  *h = (int)(u % n) + (f ? 0 : O.nf);
+}
 // the budget scalars a launch's tasks share (read once per workgroup)
 GC_DEV void selection_of(const FusedArgs& A, int64_t* n_sel, int64_t* stride) {
   *n_sel = (int64_t)A.bscal[5];
@@ -1094,14 +1112,21 @@ __device__ double g_task_wv[4 * 16384];  // per task and wave: the end of its it
 // its partial record written to rec. Ends with the workgroup synchronised (LDS free for the next task).
 // Persistent form (ctr, task_slot, ahead non-null): the next task's ticket is taken by thread 0 at the
 // start of the task's last iteration, broadcast through task_slot at the epilogue's first barrier, and
-// the next task's operands are loaded into ahead during the rest of the epilogue (T tasks, H_l
-// hypotheses: ticket t = chunk t / H_l, hypothesis t % H_l).
+// the next task's operands are loaded into ahead during the rest of the epilogue (T tasks in the
+// order ord, task_of).
 // n_sel, stride: the launch's selection (selection_of), always given by the caller. The non-look-ahead
 // persistent form measured better with it left in vector registers than moved to scalar ones (H = 256
 // 1.1568 against 1.1592 ms; profiles/r06/ab_bins_epilogue.txt).
-template <int BPL, bool FULL, bool PRE>
+// LEAN: the lean feature set (NF_LEAN, gc_binfin.h), all on the matrix core: no direction scatter, no
+// VALU moment feature, no trace complement; the record's first B * NF_LEAN + REC_EXTRA doubles. Only the
+// late-ticket instantiation of k_bins_io runs it (see there).
+// ENTM (with LEAN): the entropy partial Σ R x of a chunk without padding points on the three free MFMA
+// columns instead of 3 v_fmac_f64 per step. Long tasks only (the late-ticket instantiation): H = 256
+// 1.0621 -> 1.0504 ms per step, but the epilogue's per-bin dot made H = 32's short tasks 0.6 % slower
+// (profiles/r08/ab_bins_lean.txt).
+template <int BPL, bool FULL, bool PRE, bool LEAN = false, bool ENTM = false>
 GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double* rec, unsigned* ctr,
-                      unsigned* task_slot, TaskAhead* ahead, unsigned T, int Hl, unsigned* late_next, int bt_task,
+                      unsigned* task_slot, TaskAhead* ahead, unsigned T, const TaskOrder& ord, unsigned* late_next, int bt_task,
                       int64_t n_sel, int64_t stride) {
   (void)bt_task;
   // softmax steps per 16-lane sum and reciprocal (group16_sum2). B = 16 (one bin per lane, every lane full)
@@ -1110,19 +1135,23 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
   // which would round the product first: other bits
   constexpr int ZB = FULL && BPL == 1 ? 1 : 2;
   static_assert(kFusedUnr % ZB == 0, "the unrolled block holds whole batches");
-  constexpr int NF = NF_BASE;
+  static_assert(LEAN || !ENTM, "the entropy columns are the lean set's free ones");
+  constexpr int NF = LEAN ? NF_LEAN : NF_BASE;
   // features 0..8 and 10..16 on the matrix core, 17..18 on the VALU; feature 9 (w d_z²) is the trace
-  // complement N − w d_x² − w d_y² (write_partial_record_mfma<.., 9>): one VALU feature fewer per step
-  constexpr int DF = 9;
-  constexpr int NX = NF - 16 - 1;
-  constexpr int NS = kFusedNS;
+  // complement N − w d_x² − w d_y² (write_partial_record_mfma<.., 9>): one VALU feature fewer per step.
+  // LEAN: the 13 features on MFMA columns 0..12 in the base order; columns 13..15 read the slab's next
+  // rows (the unweighted direction: finite values, 16 distinct bank groups) and are dropped
+  constexpr int DF = LEAN ? -1 : 9;
+  constexpr int NX = LEAN ? 0 : NF - 16 - 1;
+  constexpr int NC = LEAN ? NF_LEAN : 16;
+  constexpr int NS = kFusedNS;  // the slab stride of either set (a lean slab uses its first NF_LEAN + 4 rows)
   const int64_t n_cap = A.n_cap;
   const int B = A.B;
   int iters;
   const int64_t chunk0 = chunk_first(A, c, &iters);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int g = lane >> 4, bl = lane & 15;
-  const int fcol = bl >= DF ? bl + 1 : bl;  // the feature of this lane's MFMA column
+  const int fcol = LEAN ? bl : (bl >= DF ? bl + 1 : bl);  // the slab row of this lane's MFMA column
   double* F = lds + wv * (NS * kFusedFS);
   const double o[3] = {A.o0, A.o1, A.o2};
   // the twist and iteration 0's raw point: loaded by the previous task's epilogue (persistent form), or
@@ -1146,7 +1175,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
   const double ysc = A.inv_tau * kTab2OverLn2;
   constexpr int NACC = kFusedNacc;
   v4d acc4[NACC][BPL];  // NACC = 2: even / odd steps, 2*BPL independent MFMA accumulation chains
-  double accx[BPL][NX];
+  double accx[BPL][NX > 0 ? NX : 1];
 #pragma unroll
   for (int j = 0; j < BPL; ++j) {
     acc4[0][j] = v4d{0.0, 0.0, 0.0, 0.0};
@@ -1188,6 +1217,10 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
   // exactly), bit-identical to the masked form
   auto run_iters = [&](auto pad_tag) {
     constexpr bool PAD = decltype(pad_tag)::value;
+    // ENTM without padding points: Σ_p R_pb x_pb is left to the matrix core. x_pb = L_b · d_p, and the free
+    // columns 13..15 accumulate Σ_p R_pb d_p from the slab's direction rows (the epilogue's 3-term dot per
+    // bin below). The padded form keeps the VALU sum: its padding points' directions are not zero.
+    constexpr bool kEntMfma = ENTM && !PAD;
     for (int it = 0; it < iters; ++it) {
       const int64_t wbase = chunk0 + (int64_t)it * 256 + wv * 64;
       // the next task's ticket, a whole iteration before the epilogue that broadcasts it (its round trip
@@ -1199,7 +1232,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         double p[3] = {np[0], np[1], np[2]};
         const double tt = ntt, ww = nww * scale;
         if (it + 1 < iters) fetch(it + 1);
-        double q[3], d[3], f[NF];
+        double q[3], d[3], f[NF_BASE];
         const double al = (tt - t0) * inv_denom;
         {  // six series terms when every lane of the wave has θ² <= kDeskewShortTs (wave-uniform branch)
           const double ph[3] = {al * xr[3], al * xr[4], al * xr[5]};
@@ -1210,9 +1243,14 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         direction_fast(q, o, 1e-12, d);
         point_features_w(q, d, wd, f);
         sumw += wd;
+        if constexpr (LEAN) {
+  #pragma unroll
+          for (int k = 0; k < NF; ++k) F[k * kFusedFS + lane] = f[k < 4 ? k : k + 6];  // w, w d | w p, w p pᵀ
+        } else {
   #pragma unroll
         for (int k = 0; k < NF; ++k)
           if (k != DF) F[k * kFusedFS + lane] = f[k];
+        }
         F[(NF + 0) * kFusedFS + lane] = d[0];
         F[(NF + 1) * kFusedFS + lane] = d[1];
         F[(NF + 2) * kFusedFS + lane] = d[2];
@@ -1253,6 +1291,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
         for (int j = 1; j < BPL; ++j) rm = fmax(rm, r[j]);
         // padding points (vf = 0) add nothing: S/Z scaled by 0, r >= 0 scaled to 0 under the max,
         // and log Z replaced by log 1
+        if constexpr (!kEntMfma)
   #pragma unroll
         for (int j = 0; j < BPL; ++j)  // lane partials of Σ R·x (in y units), summed over lanes at the end
           entq = fma(r[j] * vf, x[j], entq);
@@ -1317,6 +1356,7 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
           double rm = r[0];
   #pragma unroll
           for (int j = 1; j < BPL; ++j) rm = fmax(rm, r[j]);
+          if constexpr (!kEntMfma)
   #pragma unroll
           for (int j = 0; j < BPL; ++j) entq = fma(r[j] * vf, x[u][j], entq);
           mxr = fmax(mxr, rm * vf);
@@ -1356,11 +1396,20 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
   // its log. Σ log Z' (shifted by ymax) - Σ R y + ymax per valid point - B ε per point (lane 0 of
   // each wave)
   const double logacc = log_pos(zst) + (double)zex * 0.69314718055994530942;
-  const double ent = (bl == 0 ? logacc : 0.0) - entq * kExp2C1 +
-                     ((lane == 0) ? ent_shift(A.inv_tau, B) * (double)npts : 0.0);
 #pragma unroll
   for (int j = 0; j < BPL; ++j)
     if (NACC == 2) acc4[0][j] += acc4[NACC - 1][j];
+  if constexpr (ENTM) {
+    // Σ_p R_pb x_pb of a chunk without padding points (kEntMfma): lane (g, 13 + k) holds Σ_p R_pb d_pk of
+    // bins b = 16 j + g + 4 r; Lb is zero past B
+    if (chunk0 + (int64_t)iters * 256 <= n_cap && bl >= NF)
+#pragma unroll
+      for (int j = 0; j < BPL; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) entq = fma(acc4[0][j][r], Lb[(bl - NF) * 64 + 16 * j + g + 4 * r], entq);
+  }
+  const double ent = (bl == 0 ? logacc : 0.0) - entq * kExp2C1 +
+                     ((lane == 0) ? ent_shift(A.inv_tau, B) * (double)npts : 0.0);
   if (ahead) ahead->valid = false;
   // without the look-ahead (late_next): the ticket taken here, its round trip overlapping the epilogue,
   // and broadcast by the caller after it
@@ -1372,9 +1421,14 @@ GC_DEV void bins_task(const FusedArgs& A, int h, int64_t c, double* lds, double*
     if (!ctr || late_next) return;
     const unsigned tn = *task_slot;
     ahead->t = tn;
-    if (tn < T) task_operands<PRE>(A, (int)(tn % (unsigned)Hl), (int64_t)(tn / (unsigned)Hl), n_sel, stride, *ahead);
+    if (tn < T) {
+      int hn;
+      int64_t cn;
+      task_of(ord, tn, &hn, &cn);
+      task_operands<PRE>(A, hn, cn, n_sel, stride, *ahead);
+    }
   };
-  write_partial_record_mfma<BPL, NX, DF, FULL, NS * kFusedFS>(acc4[0], accx, ent, mxr, sumw, (double)npts, B, lds, rec, pre, mid);
+  write_partial_record_mfma<BPL, NX, DF, FULL, NS * kFusedFS, NC>(acc4[0], accx, ent, mxr, sumw, (double)npts, B, lds, rec, pre, mid);
   __syncthreads();  // the epilogue's LDS reads are done before the next task writes the slabs
 }
 
@@ -1434,37 +1488,56 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_io(FusedArgs A, PipeDev
     n_sel = uniform_i64(n_sel);
     stride = uniform_i64(stride);
   }
-  for (;;) {
-    // uniform: the task's record pointer lives in scalar registers (held in a VGPR it was spilled and
-    // its reload waited on the look-ahead loads issued before it)
-    const unsigned t = __builtin_amdgcn_readfirstlane(ahead.t);
-    if (t >= T) break;
-    // chunk-major: the workgroups in flight share a chunk's raw points across hypotheses (L2)
-    const int64_t c = t / H;
-    const int h = t % H;
+  // Late-ticket instantiation (long tasks): the full feature set where the hypothesis's direction scatter
+  // is read (bin_scatter_full: global hypothesis 0, the bin map's), the lean set for every other task. The
+  // full-set tasks hold the first tickets (TaskOrder): a puller runs them in a loop of their own, then the
+  // lean-set ones. The look-ahead instantiation (short tasks) runs the full set for every task, in one
+  // loop and the flat ticket order: its tasks' outputs are pinned bit for bit to recorded arrays
+  // (tests/test_gpu_bins_zbatch.py), which the lean set's two features moved to the matrix core would not
+  // keep, and two variants in that kernel spilled in its task loops (profiles/r08/bins_variants_isa.txt).
+  // The finalize writes 0.0 into a lean-set hypothesis's scatter columns from either record layout
+  // (the launch's lean_records flag), so what a caller reads does not depend on the instantiation.
+  const int nf = AHEAD ? 0 : bin_scatter_full_count(P);
+  const TaskOrder ord{(unsigned)(nf * chunks), nf, H - nf};
+  const auto pull = [&](auto lean_tag, const unsigned Tend) {
+    constexpr bool LEAN = decltype(lean_tag)::value;
+    for (;;) {
+      // uniform: the task's record pointer lives in scalar registers (held in a VGPR it was spilled and
+      // its reload waited on the look-ahead loads issued before it)
+      const unsigned t = __builtin_amdgcn_readfirstlane(ahead.t);
+      if (t >= Tend) break;
+      int h;
+      int64_t c;
+      task_of(ord, t, &h, &c);
 #ifdef GC_BINS_TIMING
-    const double tt0 = GC_BT_NOW();
+      const double tt0 = GC_BT_NOW();
 #endif
-    if constexpr (AHEAD) {
-      bins_task<BPL, FULL, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T, H,
-                                 nullptr, (int)t, n_sel, stride);
-    } else {
-      unsigned next = 0;
-      bins_task<BPL, FULL, true>(A, h, c, lds, A.partials + ((int64_t)h * chunks + c) * RL, ctr, &task_s, &ahead, T, H,
-                                 &next, (int)t, n_sel, stride);
-      if (threadIdx.x == 0) task_s = next;
-      __syncthreads();
-      ahead.t = task_s;
-    }
+      double* rec = A.partials + ((int64_t)h * chunks + c) * RL;
+      if constexpr (AHEAD) {
+        bins_task<BPL, FULL, true, LEAN>(A, h, c, lds, rec, ctr, &task_s, &ahead, T, ord, nullptr, (int)t, n_sel, stride);
+      } else {
+        unsigned next = 0;
+        bins_task<BPL, FULL, true, LEAN, LEAN>(A, h, c, lds, rec, ctr, &task_s, &ahead, T, ord, &next, (int)t, n_sel, stride);
+        if (threadIdx.x == 0) task_s = next;
+        __syncthreads();
+        ahead.t = task_s;
+      }
 #ifdef GC_BINS_TIMING
-    ++bt_n;
-    if (threadIdx.x == 0 && t < 16384) {
-      unsigned xcc = 0;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      double* g = g_task_trace + 4 * t;
-      g[0] = tt0; g[1] = GC_BT_NOW(); g[2] = (double)blockIdx.x; g[3] = (double)(xcc & 0xf);
-    }
+      ++bt_n;
+      if (threadIdx.x == 0 && t < 16384) {
+        unsigned xcc = 0;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        double* g = g_task_trace + 4 * t;
+        g[0] = tt0; g[1] = GC_BT_NOW(); g[2] = (double)blockIdx.x; g[3] = (double)(xcc & 0xf);
+      }
 #endif
+    }
+  };
+  if constexpr (AHEAD) {
+    pull(std::false_type{}, T);
+  } else {
+    pull(std::false_type{}, ord.Tf);
+    pull(std::true_type{}, T);
   }
 #ifdef GC_BINS_TIMING
   if (threadIdx.x == 0 && blockIdx.x < 8192) {
@@ -1484,7 +1557,7 @@ __global__ void __launch_bounds__(256, kFusedOcc) k_bins_fused(FusedArgs A) {
   selection_of(A, &n_sel, &stride);
   bins_task<BPL, FULL, false>(A, blockIdx.y, blockIdx.x, lds,
                               A.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * RL, nullptr, nullptr,
-                              nullptr, 0u, 1, nullptr, -1, n_sel, stride);
+                              nullptr, 0u, TaskOrder{0u, 0, 1}, nullptr, -1, n_sel, stride);
 }
 
 // ================================================================ finalize (a6 + certs)
@@ -1501,8 +1574,8 @@ GC_DEV void finalize_hyp(int h, int B, int NF, int64_t chunks, const double* __r
   const int RL = B * NF + REC_EXTRA;
   const double* P = partials + (int64_t)h * chunks * RL;
   const int imax = B * NF + 1;  // the max-responsibility entry reduces by fmax
-  if (RL <= kFinWG) finalize_reduce<1, 32>(P, RL, imax, chunks, sm);
-  else finalize_reduce<2, 16>(P, RL, imax, chunks, sm);
+  if (RL <= kFinWG) finalize_reduce<1, 32>(P, RL, RL, imax, chunks, sm);
+  else finalize_reduce<2, 16>(P, RL, RL, imax, chunks, sm);
   __syncthreads();
   double Nl = 0.0, N2l = 0.0, psdl = 0.0, epsl = 0.0, sfl = 0.0;
   if ((int)threadIdx.x < B) {
@@ -1558,7 +1631,7 @@ __global__ void __launch_bounds__(kFinSplitWG) k_bins_finalize_split(int B, int 
                                                                      const double* __restrict__ partials,
                                                                      double eps_psd, double eps_mass, double* stats,
                                                                      double* cert, double* aux, int64_t* done_word,
-                                                                     int64_t ticket) {
+                                                                     int64_t ticket, int n_full, int lean_records) {
   __shared__ double sm[kFinBins * NF_BASE + REC_EXTRA];
   // the bins launch before this one on the stream has completed, its reads of the scan slot
   // included: publish the scan's ticket to the host-coherent word the pipeline's staging checks.
@@ -1567,7 +1640,11 @@ __global__ void __launch_bounds__(kFinSplitWG) k_bins_finalize_split(int B, int 
   if (done_word && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     __hip_atomic_store(done_word, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int h = blockIdx.y, s = blockIdx.x;
-  const int RL = B * NF + REC_EXTRA;
+  const int RL = B * NF + REC_EXTRA;  // the record slot of either feature set
+  // hypotheses [0, n_full) keep their direction scatter (bin_scatter_full_count); the others' is written
+  // as 0.0, and with lean_records their records hold the lean set at the head of their slots (k_bins_io)
+  const bool zero_scatter = h >= n_full, lean = zero_scatter && lean_records;
+  if (lean) NF = NF_LEAN;
   const int b0 = s * kFinBins, nb = min(kFinBins, B - b0);
   const bool last = s == (int)gridDim.x - 1;
   const int ne = nb * NF + (last ? REC_EXTRA : 0);
@@ -1590,7 +1667,8 @@ __global__ void __launch_bounds__(kFinSplitWG) k_bins_finalize_split(int B, int 
   __syncthreads();
   if (t < nb) {
     double* ax = aux + ((int64_t)h * B + b0 + t) * 2;
-    finalize_bin(sm + t * NF, NF, eps_psd, eps_mass, stats + ((int64_t)h * B + b0 + t) * GC_BIN_STATS, ax, ax + 1);
+    finalize_bin(sm + t * NF, NF, eps_psd, eps_mass, stats + ((int64_t)h * B + b0 + t) * GC_BIN_STATS, ax, ax + 1,
+                 zero_scatter);
   } else if (last && t == 64) {
     const double* ex = sm + nb * NF;
     double* c = cert + (int64_t)h * GC_BIN_CERT;
@@ -2021,12 +2099,14 @@ int32_t scan_bins_pipeline(gc_ctx* ctx, const PipeDev& P, const ScanArgs& S, con
   if (fold && chunks <= kFoldChunks && fold_record_fits(B)) {  // k_evidence reduces the records (gc_evidence.hip)
     fold->part = (const double*)scr;
     fold->chunks = chunks;
+    fold->lean_records = !ahead;
     return GC_OK;
   }
   if (fold) fold->part = nullptr;
   const dim3 fgrid((unsigned)((B + kFinBins - 1) / kFinBins), (unsigned)H);
   hipLaunchKernelGGL(k_bins_finalize_split, fgrid, dim3(kFinSplitWG), 0, ctx->stream, B, NF, chunks,
-                     (const double*)scr, P.eps_psd, P.eps_mass, P.stats, P.bincert, P.binaux, done_word, ticket);
+                     (const double*)scr, P.eps_psd, P.eps_mass, P.stats, P.bincert, P.binaux, done_word, ticket,
+                     bin_scatter_full_count(P), ahead ? 0 : 1);
   GC_LAUNCH_CHECK(ctx);
   return GC_OK;
 }

@@ -104,6 +104,7 @@ SIGNATURES = {
     "gc_pipeline_host_stats": [_vp, _vp, _i32],
     "gc_pipeline_set_inscan_certs": [_vp, _i32],
     "gc_pipeline_set_predict_route": [_vp, _i32],
+    "gc_pipeline_set_bin_scatter_all": [_vp, _i32],
     "gc_comm_unique_id": [_vp],
     "gc_comm_init": [_vp, _i32, _i32, _vp, C.POINTER(_vp)],
     "gc_comm_destroy": [_vp],

@@ -236,6 +236,12 @@ class BatchedScanPipeline:
         formed beside the bins) or the factorised chain in the predict kernel (include/gcslam.h)."""
         self._call("gc_pipeline_set_predict_route", 1 if factorised else 0)
 
+    def set_bin_scatter_all(self, on: bool = True) -> None:
+        """Per-bin direction scatter (bin_stats()[0][..., 4:13]) for every hypothesis in later scans. Off
+        (default): only global hypothesis 0, whose scatter feeds the bin map, carries it; the other
+        hypotheses' rows hold 0.0 there and their long bin tasks accumulate 13 of the 19 moment features."""
+        self._call("gc_pipeline_set_bin_scatter_all", 1 if on else 0)
+
     def set_inscan_certs(self, on: bool = True) -> None:
         """Compute the per-hypothesis predict / fusion ConditioningCerts inside every later scan
         (right after its evidence kernel), as the reference emits them on every call."""

@@ -378,7 +378,20 @@ int32_t gc_pipeline_set_predict_route(gc_pipeline* p, int32_t route);
 /* L_evidence[pose, pose] (Hl, 6, 6) of the last scan, as the reference's MinimalScanTape.L_pose6
    (pipeline.py:1537). */
 int32_t gc_pipeline_get_lpose6(gc_pipeline* p, double* h_lpose);
+/* The last scan's bin statistics (Hl, B, GC_BIN_STATS), bin certificates (Hl, GC_BIN_CERT) and deskew
+ * twists (Hl, 6) (any pointer may be NULL). Columns 4:13 of a row, the per-bin direction scatter
+ * Σ r w d dᵀ, are computed only for global hypothesis 0 (h_begin + local index == 0) and are exactly 0.0
+ * for every other hypothesis: in the scan their only reader is the bin map's increment, which global
+ * hypothesis 0 alone feeds, so the other hypotheses' long bin tasks (32 iterations: 128 hypotheses and more at
+ * 65,536 points) accumulate 13 of the 19 moment features, and the finalize writes the zeros whichever task
+ * form ran. Every other column is computed for every hypothesis. gc_pipeline_set_bin_scatter_all brings the
+ * scatter back for all of them. */
 int32_t gc_pipeline_get_bin_stats(gc_pipeline* p, double* h_stats, double* h_cert, double* h_xi);
+/* Per-bin direction scatter for every hypothesis (off by default): with on != 0 every later scan's bin
+ * tasks accumulate all 19 moment features, and columns 4:13 of gc_pipeline_get_bin_stats are filled
+ * for every hypothesis, at the cost of the larger feature set in long tasks (a diagnostic mode; the scan's beliefs
+ * and map agree with the default's to rounding). */
+int32_t gc_pipeline_set_bin_scatter_all(gc_pipeline* p, int32_t on);
 /* Per-hypothesis statistics of the last scan (any pointer may be NULL): process-IW sufficient
  * statistics dPsi (Hl,7,6,6) and measurement-IW dPsi (Hl,3,3,3) before the weighted accumulation
  * (backend_node.py:2085-2090), and the covariance of each updated belief Σ = (L + ε_lift I)⁻¹

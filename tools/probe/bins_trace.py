@@ -3,7 +3,7 @@ a library built with -DGC_BINS_TIMING:
     mkdir -p fl-slam_amd/build_var/btime
     make -C fl-slam_amd BUILD=build_bt OUT=build_var/btime/libgcslam.so \
         CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -I../include -DGC_BINS_TIMING"
-Usage: python3 tools/probe/bins_trace.py fl-slam_amd/build_var/btime/libgcslam.so <H>"""
+Usage: python3 tools/probe/bins_trace.py fl-slam_amd/build_var/btime/libgcslam.so <H> [flat]"""
 import ctypes as C
 import os
 import sys
@@ -17,6 +17,7 @@ from gcslam import _abi  # noqa: E402
 
 _abi.LIB_PATH = os.path.abspath(sys.argv[1])
 H = sys.argv[2]
+ORDER = sys.argv[3] if len(sys.argv) > 3 else ""
 sys.argv = ["bench.py", "--hyps", H, "--no-cpu", "--no-roofline", "--no-map", "--no-c5", "--no-extras",
             "--steps", "20", "--warmup", "5"]
 import bench  # noqa: E402
@@ -58,7 +59,21 @@ tk = tk[:nT]
 Hn = int(H)
 st, en = (tk[:, 0] - t0) / 100.0, (tk[:, 1] - t0) / 100.0
 du = en - st
-ch = np.arange(nT) // Hn
+# Ticket order (TaskOrder, gc_points.hip). The late-ticket kernel runs when the tasks are 32 iterations long,
+# scan_bins_pipeline's rule: H x U >= 2 x pullers x 32 with U = 256 units of 256 points (the bench's 65,536-point
+# scans) and the pullers counted above (H >= 128 on 256 compute units). Its order: the chunks of the
+# bin_scatter_full_count full-set hypotheses first (one, hypothesis 0: the bench is unsharded and leaves
+# set_bin_scatter_all off), then the lean-set hypotheses' tasks chunk-major. Otherwise (the look-ahead kernel),
+# or with "flat" as a third argument (a library from before the lean feature set): t = chunk * H + hypothesis.
+N_FULL = 1
+long_tasks = Hn * 256 >= 2 * int(pu.sum()) * 32
+if ORDER == "flat" or not long_tasks or Hn <= N_FULL:
+    ch = np.arange(nT) // Hn
+else:
+    Tf = N_FULL * (nT // Hn)
+    ch = np.where(np.arange(nT) < Tf, np.arange(nT) // N_FULL, (np.arange(nT) - Tf) // (Hn - N_FULL))
+    du_f, du_l = du[:Tf], du[Tf:]
+    print(f"  full-set tasks {Tf} (total {du_f.sum():.0f} us), lean-set tasks {nT - Tf} (total {du_l.sum():.0f} us)")
 print(f"  tasks {nT}, chunks {ch.max() + 1}")
 for c in range(ch.max() + 1):
     sel = ch == c
