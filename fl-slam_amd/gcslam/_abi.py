@@ -157,6 +157,12 @@ SIGNATURES = {
     "gc_camera_measurement_batch": [_vp, _i64, _vp, _vp, _vp, _i64] + [_vp] * 11 + [_vp, _vp, _f64, _f64, _i32, _i32,
                                                                                     _i32, _f64] + [_vp] * 14,
     "gc_measurement_batch_from_camera_splats": [_vp, _i64] + [_vp] * 7 + [_i32, _i32, _i32, _f64] + [_vp] * 9,
+    "gc_renderable_batch_from_view": [_vp, _vp, _f64, _vp, C.POINTER(C.c_int64)],
+    "gc_bev_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "gc_render_ewa_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp],
+    "gc_splat_indices_for_tile": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _vp, C.POINTER(C.c_int32)],
+    "gc_render_tile_ewa": [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _f64, _vp],
+    "gc_fbm_at_positions": [_vp, _i64, _vp, _i32, _f64, _i64, _vp],
 }
 
 GC_PCFG_LEN = 22

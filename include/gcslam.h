@@ -1130,6 +1130,96 @@ int32_t gc_measurement_batch_from_camera_splats(gc_ctx* ctx, int64_t N, const do
                                                 int32_t* d_source_indices, uint8_t* d_valid_mask,
                                                 double* d_timestamps_out, double* d_colors);
 
+/* ------------------------------------------------------------------------------------------
+ * Rendering the map: the renderable batch, BEV splat preparation and the EWA tile raster
+ * (backend/map_publisher.py, common/bev_pushforward.py, backend/rendering.py).
+ * ------------------------------------------------------------------------------------------ */
+/* RenderablePrimitiveBatch (backend/structures/primitive_map.py:454-471) in device memory, plus the
+   recency it was ordered by. The caller allocates every array for the view's V entries. */
+typedef struct gc_render_batch {
+  int32_t n_lobes;
+  int32_t pad_;
+  double* mu_world;                 /* (V, 3) */
+  double* Sigma_world;              /* (V, 3, 3) */
+  double* Lambda_world;             /* (V, 3, 3) inv(Sigma_world + eps_lift I) */
+  double* eta;                      /* (V, n_lobes, 3) */
+  double* mass;                     /* (V) */
+  double* color;                    /* (V, 3) the view's colors (the map's rgb) */
+  int64_t* primitive_ids;           /* (V) */
+  int64_t* last_supported_scan_seq; /* (V) */
+} gc_render_batch;
+
+/* PrimitiveMapPublisher.publish (backend/map_publisher.py:143-242) from a map view: the entries with
+   valid_mask, in the order np.lexsort((primitive_ids, -last_supported_scan_seq)) (:200: newest first,
+   ties by ascending primitive id), compacted into rows [0, count); every row from count on is zero.
+   Lambda_world = inv(Sigma_world + eps_lift I) (:232-233). h_count (host) receives count: the one
+   wait. Primitive ids and sequence numbers must be below 2^53 in magnitude (they are sorted as double
+   keys). An empty view (V = 0, or no valid entry) gives count = 0; V = 0 launches nothing.
+   GC_ERR_ARG for n_lobes outside [1, 8] or unequal in view and batch, V >= 2^31 or NULL pointers. */
+int32_t gc_renderable_batch_from_view(gc_ctx* ctx, const gc_map_view* view, double eps_lift, const gc_render_batch* out,
+                                      int64_t* h_count);
+
+#define GC_BEV_CFG_LEN 11 /* [origin_x, origin_y, px_per_m, eps, opacity_gamma, logdet0, alpha_min, fbm_octaves,
+                             fbm_gain, fbm_seed, fbm_modulate_scale] (the viewport, SplatRenderingConfig
+                             rendering.py:28-44, and render_tile_ewa's fbm arguments :307-310) */
+/* The 2D splats of n_views views of n primitives, view-major. The caller allocates every array. */
+typedef struct gc_bev_splats {
+  double* means_px;   /* (n_views, n, 2) column, row */
+  double* Sigmas_inv; /* (n_views, n, 2, 2) */
+  double* alphas;     /* (n_views, n) */
+  double* colors;     /* (n_views, n, 3) */
+  double* fbm;        /* (n) */
+  double* Sigmas_bev; /* (n_views, n, 2, 2) P Sigma P^T itself; may be NULL */
+} gc_bev_splats;
+
+/* Rows [0, n) of a batch as 2D splats, per view v with h_P[v] (2, 3) and h_view_dirs[v] (3) (host):
+   mu_bev = P mu, Sigma_bev = (P Sigma) P^T (pushforward_gaussian_3d_to_2d, bev_pushforward.py:59-64);
+   means_px = (mu_bev - origin_xy) px_per_m; Sigmas_inv = the closed-form inverse of
+   px_per_m^2 Sigma_bev + eps I; alphas = opacity_from_logdet(log det Sigma_bev) (rendering.py:236-244);
+   colors = color * vmf_shading_multi_lobe(view_dir, eta, |eta|) * ((1 - s_f) + s_f fbm) with uniform
+   lobe weights and no intensity (:117-159, :333-340); fbm = fbm_value_noise at the primitive's world
+   (x, y) (:167-209). The integer hash of the noise is the reference's while
+   |coordinate| * 2^(octaves - 1) < 2^31. No wait. GC_ERR_ARG for n outside [0, 2^24], n_views outside
+   [1, 32], n_lobes outside [1, 8], px_per_m <= 0, fbm_octaves not an integer in [0, 32], fbm_seed not
+   an integer in [0, 2^31), a non-finite host value or NULL pointers. */
+int32_t gc_bev_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_P,
+                          const double* h_view_dirs, const double* h_cfg, const gc_bev_splats* out);
+
+/* splat_indices_for_tile (rendering.py:252-289) for every tile of every view, then render_tile_ewa
+   (:297-355) over each tile's list. Tiles are row-major, T = (H / tile_size) (W / tile_size) per view;
+   tile (ty, tx) has origin (ty tile_size, tx tile_size). A splat is kept where none of the four bbox
+   comparisons with r = 2 / sqrt(max(lambda_min(Sigma_inv), eps)) rejects it; the kept ones are ordered
+   by dist_sq to the tile centre, ties by splat index, and the first cap are taken: d_tile_counts
+   (n_views, T) and d_tile_indices (n_views, T, cap), -1 past the count. d_images (n_views, H, W, 3):
+   per pixel centre (column + 0.5, row + 0.5) the sums of w_i c_i and w_i with
+   w_i = alpha_i exp(clip(-q_i / 2, -log_clip, 0)), in list order, divided by (sum w + 1e-12) where that
+   exceeds 1e-12 and clipped to [0, 1]. Bitwise reproducible. No wait. n = 0: zero images and counts,
+   no kernel. GC_ERR_ARG for tile_size outside [1, 32], H or W not a multiple of tile_size in
+   [1, 16384], cap outside [1, 256], n < 0, n_views outside [1, 32], n_views * T * n >= 2^32 or NULL
+   pointers. */
+int32_t gc_render_ewa_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_bev_splats* splats, int32_t H, int32_t W,
+                            int32_t tile_size, int32_t cap, double log_clip, double eps, double* d_images,
+                            int32_t* d_tile_counts, int32_t* d_tile_indices);
+
+/* splat_indices_for_tile (rendering.py:252-289) for one tile at any origin: d_indices receives
+   min(cap, n) entries (-1 past the count), h_count (host) the count: one wait. */
+int32_t gc_splat_indices_for_tile(gc_ctx* ctx, int64_t n, const double* d_means, const double* d_Sigmas_inv,
+                                  int32_t origin_y, int32_t origin_x, int32_t tile_size, int32_t cap, double eps,
+                                  int32_t* d_indices, int32_t* h_count);
+
+/* render_tile_ewa (rendering.py:297-355) for one tile at any origin over the n_idx splats d_indices
+   (int32, each clamped into [0, n)) in that order; n_idx = -1: every splat in index order. d_image
+   (tile_size, tile_size, 3). n = 0 or n_idx = 0: a zero image (:324-327). No wait. */
+int32_t gc_render_tile_ewa(gc_ctx* ctx, int64_t n, const double* d_means, const double* d_Sigmas_inv,
+                           const double* d_alphas, const double* d_colors, int32_t origin_y, int32_t origin_x,
+                           int32_t tile_size, const int32_t* d_indices, int64_t n_idx, double log_clip,
+                           double* d_image);
+
+/* fbm_at_splat_positions (rendering.py:212-228): d_out (n) from d_xy (n, 2). Domain of the integer
+   hash as in gc_bev_splat_prep. No wait. */
+int32_t gc_fbm_at_positions(gc_ctx* ctx, int64_t n, const double* d_xy, int32_t octaves, double gain, int64_t seed,
+                            double* d_out);
+
 #ifdef __cplusplus
 }
 #endif
