@@ -26,7 +26,6 @@ namespace {
 constexpr int kMaxK = 16;          // k_assoc supported
 constexpr int kMaxStencil = 128;   // n_z * n_xy stencil tiles per row
 constexpr int kSinkT = 1024;       // Sinkhorn workgroup
-constexpr int kMaxLobesA = 8;
 
 struct OTCfg {
   int K, iters, row_min, wprop, r_xy, r_z;
@@ -126,11 +125,6 @@ GC_DEV double ot_cost1(const double* mp, const double* md, double mk, const doub
   return dpos + beta * ddir;
 }
 
-GC_DEV int64_t pack_tile(int64_t c1, int64_t c2, int64_t cz) {
-  constexpr int64_t b = 1 << 20, m = (1 << 21) - 1;
-  return (((c1 + b) & m) << 42) | (((c2 + b) & m) << 21) | ((cz + b) & m);
-}
-
 GC_DEV bool key_less(double ca, int pa, double cb, int pb) { return ca < cb || (ca == cb && pa < pb); }
 
 // one wave per measurement row; 4 rows per 256-thread workgroup
@@ -146,9 +140,8 @@ __global__ void __launch_bounds__(256) k_assoc_rows(int64_t N, int L, const doub
   if (i >= N) return;  // whole wave exits together (no workgroup barrier below)
   const int K = c.K, kv = V.m_tile_view;
   // measurement mean position / direction / kappa (measurement_batch.py:389-411)
-  double Lr[9], mp[3], es[3] = {0, 0, 0};
-  for (int q = 0; q < 9; ++q) Lr[q] = Lam[9 * i + q] + ((q % 4 == 0) ? c.eps_lift : 0.0);
-  solve3(Lr, tht + 3 * i, mp);
+  double mp[3], es[3] = {0, 0, 0};
+  prim_mean(Lam + 9 * i, tht + 3 * i, c.eps_lift, mp);
   for (int l = 0; l < L; ++l)
     for (int q = 0; q < 3; ++q) es[q] += eta[(i * L + l) * 3 + q];
   const double mk = sqrt(es[0] * es[0] + es[1] * es[1] + es[2] * es[2]);
@@ -431,7 +424,7 @@ int32_t gc_extract_map_view(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_
   }
   const int T = view->n_tiles, k = view->m_tile_view;
   GC_CHECK_ARG(ctx, T >= 1 && k >= 1 && m_tile >= k && m_tile < (int64_t)INT32_MAX, "bad view shape");
-  GC_CHECK_ARG(ctx, view->n_lobes == map->n_lobes && map->n_lobes <= kMaxLobesA, "n_lobes mismatch");
+  GC_CHECK_ARG(ctx, view->n_lobes == map->n_lobes && map->n_lobes <= kMapMaxLobes, "n_lobes mismatch");
   GC_CHECK_ARG(ctx, map->valid_mask && map->Lambdas && map->thetas && map->etas && map->weights &&
                         map->last_supported_scan_seq,
                "NULL map field");
@@ -480,7 +473,7 @@ int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, cons
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, view && h_cfg && h_cert_out, "NULL argument");
-  GC_CHECK_ARG(ctx, N >= 1 && n_lobes >= 1 && n_lobes <= kMaxLobesA, "bad N or n_lobes");
+  GC_CHECK_ARG(ctx, N >= 1 && n_lobes >= 1 && n_lobes <= kMapMaxLobes, "bad N or n_lobes");
   GC_CHECK_ARG(ctx, d_Lambdas && d_thetas && d_etas && d_valid && d_resp_out && d_cand_out && d_cand_tile_out &&
                         d_cand_slot_out && d_row_mass_out && d_cost_out,
                "NULL buffer");

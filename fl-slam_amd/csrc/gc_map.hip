@@ -35,9 +35,8 @@ struct FuseArgs {
   int col32;  // rgb (and colors) at their layout offsets: written as whole 32-B sectors (slot_colour32)
 };
 
-// One measurement row in the world frame (pipeline.py:1248-1256): Λ_w = R Λ Rᵀ,
-// μ_b = (Λ + ε I)⁻¹ θ, μ_w = R μ_b + t, θ_w = Λ_w μ_w, η_w = R η (each lobe). Lb / tb / eb: the row's
-// Λ (9), θ (3) and η (3L), in HBM or staged in LDS.
+// One measurement row in the world frame (gaussian_to_world), or as it is when the fuse has no pose. Lb / tb /
+// eb: the row's Λ (9), θ (3) and η (3L), in HBM or staged in LDS.
 template <int LT>  // LT > 0: the lobe count at compile time (registers, no scratch); 0: A.map.n_lobes
 GC_DEV void meas_world(const FuseArgs& A, const double* R, const double* Lb, const double* tb, const double* eb,
                        double* Lw, double* th, double* et) {
@@ -48,18 +47,8 @@ GC_DEV void meas_world(const FuseArgs& A, const double* R, const double* Lb, con
     for (int q = 0; q < 3 * L; ++q) et[q] = eb[q];
     return;
   }
-  double M3[9], Lr[9], mu[3], mw[3];
-  mat3_mul(R, Lb, M3);
-  mat3_mul_nt(M3, R, Lw);
-  for (int q = 0; q < 9; ++q) Lr[q] = Lb[q] + ((q % 4 == 0) ? A.eps_lift : 0.0);
-  solve3(Lr, tb, mu);
-  mat3_vec(R, mu, mw);
-  for (int q = 0; q < 3; ++q) mw[q] += A.pose[q];
-  mat3_vec(Lw, mw, th);
-  for (int l = 0; l < L; ++l) mat3_vec(R, eb + 3 * l, et + 3 * l);
+  gaussian_to_world(R, A.pose, A.eps_lift, L, Lb, tb, eb, Lw, th, et);
 }
-
-constexpr int kMaxLobes = 8;
 
 // A measurement row's contribution, formed exactly as the reference forms it before its scatter-add
 // (r * X, primitive_map.py:1074-1095): [r Λ_w 9 | r θ_w 3 | r η_w 3L | r w | r | w_cam | w_lidar |
@@ -71,7 +60,7 @@ template <int LT>
 GC_DEV void row_terms_at(const FuseArgs& A, const double* R, const double* Lb, const double* tb, const double* eb,
                          double r, double wm, int src, const double* col, double* o) {
 #pragma clang fp contract(off)  // the products rounded as the reference's r * X
-  constexpr int LM = LT > 0 ? LT : kMaxLobes;
+  constexpr int LM = LT > 0 ? LT : kMapMaxLobes;
   const int L = LT > 0 ? LT : A.map.n_lobes;
   double Lw[9], th[3], et[3 * LM];
   meas_world<LT>(A, R, Lb, tb, eb, Lw, th, et);
@@ -102,20 +91,6 @@ GC_DEV void row_terms(const FuseArgs& A, const double* R, int64_t k, double* o) 
   const int src = A.meas.sources ? A.meas.sources[k] : -1;
   row_terms_at<LT>(A, R, A.meas.Lambdas + 9 * k, A.meas.thetas + 3 * k, A.meas.etas + (int64_t)3 * L * k,
                    row_r(A, k), A.meas.weights[k], src, A.meas.colors ? A.meas.colors + 3 * k : nullptr, o);
-}
-
-// rgb of one slot from its camera accumulators (primitive_map.py:1090-1098): clip(accum / max(denom,
-// ε), 0, 1) where cam_mass > 0, else gray; colors = rgb
-GC_DEV void slot_colour(const gc_primitive_map& m, int64_t s, double cam, const double* acc, double denom,
-                        double eps_mass) {
-  const bool on = cam > 0.0;
-  const double den = fmax(denom, eps_mass);
-  double* rgb = mRgb(m, s);
-  for (int q = 0; q < 3; ++q) {
-    const double v = on ? clampd(acc[q] / den, 0.0, 1.0) : 0.5;
-    rgb[q] = v;
-    if (m.colors) mCol(m, s)[q] = v;
-  }
 }
 
 // ---- pass 1: per block of kFuseBlk rows (one per thread), the (slot, row) sort and the run entries
@@ -198,10 +173,8 @@ GC_DEV void fuse_apply_slot(const FuseArgs& A, int64_t s, const double* d) {
 GC_DEV void slot_colour32(const gc_primitive_map& m, int64_t s, double cam, const double* acc, double denom,
                           double eps_mass) {
   typedef double dvec2 __attribute__((ext_vector_type(2)));
-  const bool on = cam > 0.0;
-  const double den = fmax(denom, eps_mass);
   double v[3];
-  for (int q = 0; q < 3; ++q) v[q] = on ? clampd(acc[q] / den, 0.0, 1.0) : 0.5;
+  slot_colour_value(cam, acc, denom, eps_mass, v);
   dvec2* rgb = reinterpret_cast<dvec2*>(mRgb(m, s));
   rgb[0] = dvec2{v[0], v[1]};
   rgb[1] = dvec2{v[2], 0.0};
@@ -248,6 +221,33 @@ GC_DEV void fuse_apply_rec32(const FuseArgs& A, int64_t s, double* rec, const do
   }
 }
 
+// The owner's walk over its slot's runs in block order: the run at p alone when the slot's rows all lie in
+// one block (s1 == 0, the common case), else the chain from p collected into rl.
+template <int CAP, typename AddRun>
+GC_DEV void walk_runs(SlotRunList<CAP>& rl, uint32_t p, uint32_t s1, uint32_t* succ, int n_blocks, AddRun add_run) {
+  if (s1 == 0u) {
+    add_run(p);
+    return;
+  }
+  rl.collect(p, s1, succ, n_blocks);
+  uint32_t prev = 0;
+  for (int i = 0; i < rl.n; ++i) {  // runs in block order
+    const uint32_t r = rl.at(i, prev);
+    if (r == kNoRun) break;  // only a corrupt entry: never index past the runs
+    prev = r;
+    add_run(r);
+  }
+}
+
+// the distinct-slot count per workgroup (an LDS sum: one global counter for every wave serialised the
+// kernel's end); *owned was zeroed before a barrier
+GC_DEV void count_owned(bool own, uint32_t* owned, uint32_t* wg_count) {
+  const unsigned long long b = __ballot(own);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(owned, (uint32_t)__popcll(b));
+  __syncthreads();
+  if (threadIdx.x == 0) wg_count[blockIdx.x] = *owned;
+}
+
 // one thread per sorted position; the owner of each slot (the run its list ends on) fuses the slot
 template <int LT>
 __global__ void __launch_bounds__(kApplyWG) k_fuse_apply(FuseArgs A, int64_t K, RunTable T,
@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(kApplyWG) k_fuse_apply(FuseArgs A, int64_t K, 
                                                     const uint32_t* __restrict__ rank,
                                                     uint32_t* wg_count) {
 #pragma clang fp contract(off)
-  constexpr int LM = LT > 0 ? LT : kMaxLobes;
+  constexpr int LM = LT > 0 ? LT : kMapMaxLobes;
   constexpr int NT = row_terms_len(LM);
   const int64_t wgid = xcd_block(blockIdx.x, gridDim.x);  // a sort block's workgroups on one XCD
   const int64_t p = wgid * blockDim.x + threadIdx.x;
@@ -284,31 +284,15 @@ __global__ void __launch_bounds__(kApplyWG) k_fuse_apply(FuseArgs A, int64_t K, 
     __shared__ uint32_t slices[kApplyWG * kRunCap];
     SlotRunList<kRunCap> rl(slices + threadIdx.x * kRunCap);
     const uint32_t s1 = T.succ[p];
-    if (s1 == 0u) {  // the slot's rows all lie in one block (the common case)
-      add_run((uint32_t)p);
-    } else {
-      rl.collect((uint32_t)p, s1, T.succ, (int)((K + kFuseBlk - 1) / kFuseBlk));
-      uint32_t prev = 0;
-      for (int i = 0; i < rl.n; ++i) {  // runs in block order
-        const uint32_t r = rl.at(i, prev);
-        if (r == kNoRun) break;  // only a corrupt entry: never index past the runs
-        prev = r;
-        add_run(r);
-      }
-    }
+    walk_runs(rl, (uint32_t)p, s1, T.succ, (int)((K + kFuseBlk - 1) / kFuseBlk), add_run);
     fuse_apply_slot<LT>(A, s, d);
     if (s1 != 0u) rl.clear();
     T.e[rank[p]] = 0ull;  // the entry and the chain empty for the next call
   }
-  // the distinct-slot count per workgroup (an LDS sum: one global counter for every wave serialised
-  // the kernel's end)
   __shared__ uint32_t owned;
   if (threadIdx.x == 0) owned = 0u;
   __syncthreads();
-  const unsigned long long b = __ballot(own);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&owned, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (threadIdx.x == 0) wg_count[blockIdx.x] = owned;
+  count_owned(own, &owned, wg_count);
 }
 
 // The packed 3-lobe record's apply with the rows staged: one workgroup per sort block (kFuseBlk
@@ -428,18 +412,7 @@ __global__ void __launch_bounds__(kFuseBlk) k_fuse_apply_blk(FuseArgs A, int64_t
       }
     };
     SlotRunList<kBlkRunCap> rl(slices + t * kBlkRunCap);
-    if (s1 == 0u) {
-      add_run((uint32_t)p);
-    } else {
-      rl.collect((uint32_t)p, s1, T.succ, (int)((K + NB - 1) / NB));
-      uint32_t prev = 0;
-      for (int i = 0; i < rl.n; ++i) {
-        const uint32_t r = rl.at(i, prev);
-        if (r == kNoRun) break;
-        prev = r;
-        add_run(r);
-      }
-    }
+    walk_runs(rl, (uint32_t)p, s1, T.succ, (int)((K + NB - 1) / NB), add_run);
     double rec[32];
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
@@ -449,10 +422,7 @@ __global__ void __launch_bounds__(kFuseBlk) k_fuse_apply_blk(FuseArgs A, int64_t
     fuse_apply_rec32(A, s, rec, d);
     if (s1 != 0u) rl.clear();
   }
-  const unsigned long long b = __ballot(own);
-  if ((t & 63) == 0 && b) atomicAdd(&owned, (uint32_t)__popcll(b));
-  __syncthreads();
-  if (t == 0) wg_count[blockIdx.x] = owned;
+  count_owned(own, &owned, wg_count);
 }
 
 // every slot's colour estimate (primitive_map.py:1090-1098)
@@ -522,10 +492,8 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
     int64_t off[gc::kRecFields], sb = 0;
     gc::map_record_layout(3, off, &sb);
     const char* b0 = (const char*)map->Lambdas;
-    const void* f[gc::kRecFields] = {map->Lambdas, map->thetas, map->etas, map->weights, map->timestamps,
-                                     map->last_supported_scan_seq, map->last_update_scan_seq, map->cam_mass,
-                                     map->lidar_mass, map->rgb_cam_accum, map->rgb_cam_denom, map->rgb,
-                                     map->colors, map->valid_mask, map->created_timestamps, map->primitive_ids};
+    const void* f[gc::kRecFields];
+    gc::map_fields(*map, f);
     bool ok = map->n_lobes == 3 && map->slot_bytes == sb && ((uintptr_t)b0 % 16) == 0;
     for (int q = 0; q < 7 && ok; ++q) ok = (const char*)f[q] - b0 == off[q];  // the fuse's fields
     for (int q = 7; q < 11 && ok; ++q) ok = f[q] == nullptr || (const char*)f[q] - b0 == off[q];
@@ -583,18 +551,7 @@ int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, map && meas, "NULL map or measurement batch");
-  GC_CHECK_ARG(ctx, map->m_slots > 0 && map->m_slots < (int64_t)kDropped, "m_slots out of range");
-  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobes, "n_lobes must be in [1, 8]");
-  {
-    const char* lay_ = gc::map_layout_error(*map);
-    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
-  }
-  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
-                        map->last_supported_scan_seq && map->last_update_scan_seq,
-               "NULL map field");
-  const bool color = map->cam_mass != nullptr;
-  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
-               "colour fields must be all set or all NULL");
+  if (int rc = gc::check_map(ctx, map, (int64_t)kDropped, false)) return rc;
   GC_CHECK_ARG(ctx, meas->K >= 0 && meas->K < (int64_t)kDropped, "K out of range");
   if (n_fused_out) *n_fused_out = 0;
   const int64_t K = meas->K;
@@ -620,7 +577,7 @@ int32_t gc_primitive_map_fuse(gc_ctx* ctx, const gc_primitive_map* map, const gc
 }
 
 int32_t gc_primitive_map_record_layout(int32_t n_lobes, int64_t* offsets_out, int64_t* slot_bytes_out) {
-  GC_CHECK_ARG(nullptr, n_lobes >= 1 && n_lobes <= kMaxLobes, "n_lobes must be in [1, 8]");
+  GC_CHECK_ARG(nullptr, n_lobes >= 1 && n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
   GC_CHECK_ARG(nullptr, offsets_out && slot_bytes_out, "NULL output");
   gc::map_record_layout(n_lobes, offsets_out, slot_bytes_out);
   return GC_OK;

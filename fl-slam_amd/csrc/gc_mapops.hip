@@ -15,9 +15,10 @@
 // inherently sequential and runs on one lane over the sorted candidates, stopping at the first
 // distance >= threshold.
 //
-// gc_primitive_map_maintain (backend/pipeline.py:1412-1447) runs cull, forget and merge-reduce over
-// all active tiles with no host wait: the same per-slot bodies with the tile in the grid, the
-// entries' host decisions as per-tile predicates in device memory, one segmented sort per phase.
+// There is one kernel family, over a span of tiles with the tile in blockIdx.y (Tiles). A per-tile entry
+// launches it on a span of one tile, waits for its counts and decides on the host what runs next.
+// gc_primitive_map_maintain (backend/pipeline.py:1412-1447) launches it over all active tiles with no host
+// wait: the entries' host decisions are per-tile predicates in device memory, one segmented sort per phase.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
@@ -31,7 +32,6 @@
 namespace gc {
 namespace {
 
-constexpr int kMaxLobesOps = 8;
 constexpr int kPartBlocks = 240;  // grid of the reduction passes (<= one wave of workgroups)
 constexpr int64_t kMaintainGroupTiles = GC_MAP_MAINTAIN_GROUP_TILES;
 
@@ -39,6 +39,27 @@ struct Tile {
   gc_primitive_map m;
   int64_t s0, n;
 };
+
+// What the maintenance kernels run over: tiles of n slots, tile a (blockIdx.y, or the a-th of a group)
+// starting at slot s0 + dense[a] * n. A per-tile entry passes its own range as a span of one tile
+// (dense = NULL, any s0); the passes over the active tiles pass s0 = 0 and the dense tile list. What the
+// per-tile entries decide on the host, those passes read from the device statistics (kStats doubles per
+// active tile).
+constexpr int kStats = GC_MAP_MAINTAIN_STATS_TILE;
+static_assert(kStats == 8, "the statistics row is written by index below");
+
+struct Tiles {
+  gc_primitive_map m;
+  int64_t s0, n;
+  const int32_t* dense;
+};
+GC_DEV Tile tile_of(const Tiles& S, int64_t a) {
+  return Tile{S.m, S.s0 + (S.dense ? (int64_t)S.dense[a] * S.n : 0), S.n};
+}
+// whether tile a's merge runs; NULL: the caller has decided on the host that it does
+GC_DEV bool merge_runs(const double* __restrict__ stats, int64_t a) {
+  return !stats || stats[kStats * a + 7] == (double)GC_MAP_MAINTAIN_MERGE_RAN;
+}
 
 // Fixed-order block sum of NV per-thread values into part[blockIdx.x * NV + v]. The wave step is the
 // butterfly of gc_blocksum.h; the four waves are added pairwise, (w0 + w1) + (w2 + w3), not in
@@ -58,12 +79,14 @@ GC_DEV void block_partials(double (&v)[NV], double* part) {
         (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
+// the blocks' partials of tile blockIdx.x added in block order by one thread per value: out[a * NV + v]
 template <int NV>
 __global__ void k_sum_parts(const double* __restrict__ part, int blocks, double* out) {
   if ((int)threadIdx.x >= NV) return;
+  const double* p = part + (size_t)blockIdx.x * blocks * NV;
   double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += part[b * NV + threadIdx.x];
-  out[threadIdx.x] = s;
+  for (int b = 0; b < blocks; ++b) s += p[b * NV + threadIdx.x];
+  out[blockIdx.x * NV + threadIdx.x] = s;
 }
 
 __global__ void k_forget(Tile T, double gamma) {
@@ -97,11 +120,12 @@ GC_DEV void recency_slots(const Tile& T, int64_t seq, double lam, double min_sca
   }
 }
 
-// part: [n_valid, Σ(1 - decay), Σ(1/decay - 1)] over valid slots
-__global__ void __launch_bounds__(256) k_recency(Tile T, int64_t seq, double lam, double min_scale, double* part) {
+// the tile in blockIdx.y; its partials [n_valid, Σ(1 - decay), Σ(1/decay - 1)] over valid slots at
+// part + a * gridDim.x * 3
+__global__ void __launch_bounds__(256) k_recency(Tiles S, int64_t seq, double lam, double min_scale, double* part) {
   double acc[3] = {0.0, 0.0, 0.0};
-  recency_slots(T, seq, lam, min_scale, acc);
-  block_partials<3>(acc, part);
+  recency_slots(tile_of(S, blockIdx.y), seq, lam, min_scale, acc);
+  block_partials<3>(acc, part + (size_t)blockIdx.y * gridDim.x * 3);
 }
 
 // one slot's terms of [n_valid, n_below, mass_below, Σ w (all slots)]; returns whether the slot is culled at thr
@@ -117,31 +141,38 @@ GC_DEV bool cull_count_slot(const Tile& T, int64_t s, double thr, double (&acc)[
   return below;
 }
 
-// part: [n_valid, n_below, mass_below, Σ w (all slots)]
-__global__ void __launch_bounds__(256) k_cull_count(Tile T, double thr, double* part) {
+// The count of the tile in blockIdx.y at its threshold thr_a[a] (NULL: thr0): partials [n_valid, n_below,
+// mass_below, Σ w (all slots)] at part + a * gridDim.x * 4. CULL: the slot is also culled in the same visit,
+// FORGET: and forgotten (w *= gamma), which no other slot's result depends on. Without FORGET no weight is
+// stored.
+template <bool CULL, bool FORGET>
+__global__ void __launch_bounds__(256) k_cull(Tiles S, double thr0, const double* __restrict__ thr_a, double gamma,
+                                              double* part) {
+  const Tile T = tile_of(S, blockIdx.y);
+  const double thr = thr_a ? thr_a[blockIdx.y] : thr0;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x)
-    cull_count_slot(T, s, thr, acc);
-  block_partials<4>(acc, part);
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x) {
+    const bool below = cull_count_slot(T, s, thr, acc);
+    if (CULL && below) mValid(T.m, T.s0 + s) = 0;
+    if (FORGET) mW(T.m, T.s0 + s) = gamma * mW(T.m, T.s0 + s);
+  }
+  block_partials<4>(acc, part + (size_t)blockIdx.y * gridDim.x * 4);
 }
 
-__global__ void k_cull_keys(Tile T, double* keys) {
+// keys[a * n + s] = w · valid of slot s of the tile in blockIdx.y
+__global__ void k_cull_keys(Tiles S, double* keys) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < T.n) keys[s] = mW(T.m, T.s0 + s) * (mValid(T.m, T.s0 + s) ? 1.0 : 0.0);
+  if (s >= S.n) return;
+  const Tile T = tile_of(S, blockIdx.y);
+  keys[(int64_t)blockIdx.y * S.n + s] = mW(T.m, T.s0 + s) * (mValid(T.m, T.s0 + s) ? 1.0 : 0.0);
 }
 
-__global__ void k_cull_apply(Tile T, double thr) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= T.n) return;
-  const int64_t g = T.s0 + s;
-  if (mValid(T.m, g) && mW(T.m, g) < thr) mValid(T.m, g) = 0;
-}
-
-__global__ void __launch_bounds__(256) k_count_valid(Tile T, double* part) {
+__global__ void __launch_bounds__(256) k_count_valid(Tiles S, double* part) {
+  const Tile T = tile_of(S, blockIdx.y);
   double acc[1] = {0.0};
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x)
     acc[0] += mValid(T.m, T.s0 + s) ? 1.0 : 0.0;
-  block_partials<1>(acc, part);
+  block_partials<1>(acc, part + (size_t)blockIdx.y * gridDim.x);
 }
 
 // eviction key (_select_lowest_mass_slots_fixed): retention w·exp(-λ dt) on valid slots, -inf on
@@ -223,15 +254,20 @@ __global__ void __launch_bounds__(256) k_insert_apply(Tile T, gc_insert_batch B,
 GC_DEV void merge_prep_slot(const Tile& T, int64_t s, double eps_lift, double* mu, double* Sig, double* dets) {
   const int64_t g = T.s0 + s;
   double Lr[9];
-  for (int q = 0; q < 9; ++q) Lr[q] = mLam(T.m, g)[q] + ((q % 4 == 0) ? eps_lift : 0.0);
+  lifted3(mLam(T.m, g), eps_lift, Lr);
   solve3(Lr, mTh(T.m, g), mu + 3 * s);
   inv3(Lr, Sig + 9 * s);
   dets[s] = det3(Sig + 9 * s);
 }
 
-__global__ void k_merge_prep(Tile T, double eps_lift, double* mu, double* Sig, double* dets) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < T.n) merge_prep_slot(T, s, eps_lift, mu, Sig, dets);
+// The merge kernels run on the tiles a0 .. a0 + g - 1 of the span, the tile of the group in blockIdx.y (one
+// workgroup per tile for the select); mu / Sig / dets / used hold n slots per tile of the group, keys / vals
+// P pairs, sel max_pairs pairs, n_sel one count per tile of the span.
+__global__ void k_merge_prep(Tiles S, int64_t a0, const double* __restrict__ stats, double eps_lift, double* mu,
+                             double* Sig, double* dets) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
+  if (s >= S.n || !merge_runs(stats, a0 + la)) return;
+  merge_prep_slot(tile_of(S, a0 + la), s, eps_lift, mu + 3 * la * S.n, Sig + 9 * la * S.n, dets + la * S.n);
 }
 
 // pair p of jnp.triu_indices(n, k=1) (row-major, i < j)
@@ -265,12 +301,16 @@ GC_DEV double merge_pair_dist(const Tile& T, int64_t p, const double* __restrict
   return pv ? quad + logt : INFINITY;
 }
 
-__global__ void k_merge_dist(Tile T, int64_t P, const double* __restrict__ mu, const double* __restrict__ Sig,
+__global__ void k_merge_dist(Tiles S, int64_t a0, int64_t P, const double* __restrict__ stats,
+                             const double* __restrict__ mu, const double* __restrict__ Sig,
                              const double* __restrict__ dets, double eps_lift, double* keys, uint32_t* vals) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
   if (p >= P) return;
-  keys[p] = merge_pair_dist(T, p, mu, Sig, dets, eps_lift);
-  vals[p] = (uint32_t)p;
+  const int64_t x = la * P + p;
+  vals[x] = (uint32_t)p;
+  keys[x] = merge_runs(stats, a0 + la) ? merge_pair_dist(tile_of(S, a0 + la), p, mu + 3 * la * S.n,
+                                                         Sig + 9 * la * S.n, dets + la * S.n, eps_lift)
+                                       : INFINITY;
 }
 
 // greedy disjoint selection over the sorted candidates (_merge_reduce_jax select_body), one lane
@@ -294,10 +334,13 @@ GC_DEV int merge_select_walk(int64_t n, int64_t P, const double* __restrict__ ke
   return ns;
 }
 
-__global__ void k_merge_select(int64_t n, int64_t P, const double* __restrict__ keys, const uint32_t* __restrict__ vals,
-                               double thr, int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  *n_sel = merge_select_walk(n, P, keys, vals, thr, max_pairs, used, sel);
+__global__ void k_merge_select(int64_t n, int64_t a0, int64_t P, const double* __restrict__ stats,
+                               const double* __restrict__ keys, const uint32_t* __restrict__ vals, double thr,
+                               int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
+  const int64_t la = blockIdx.x;
+  if (threadIdx.x != 0 || !merge_runs(stats, a0 + la)) return;
+  n_sel[a0 + la] = merge_select_walk(n, P, keys + la * P, vals + la * P, thr, max_pairs, used + la * n,
+                                     sel + la * 2 * max_pairs);
 }
 
 // moment-matched merge of the pair (i, j) into slot i (_merge_reduce_jax merge_body)
@@ -332,13 +375,9 @@ GC_DEV void merge_apply_pair(const Tile& T, const double* __restrict__ mu, const
     mCam(T.m, gi) = cm;
     mLid(T.m, gi) = mLid(T.m, gi) + mLid(T.m, gj);
     mDen(T.m, gi) = den;
-    for (int q = 0; q < 3; ++q) {
-      const double acc = mAcc(T.m, gi)[q] + mAcc(T.m, gj)[q];
-      const double rgb = cm > 0.0 ? clampd(acc / fmax(den, eps_psd), 0.0, 1.0) : 0.5;
-      mAcc(T.m, gi)[q] = acc;
-      mRgb(T.m, gi)[q] = rgb;
-      if (T.m.colors) mCol(T.m, gi)[q] = rgb;
-    }
+    double acc[3];
+    for (int q = 0; q < 3; ++q) mAcc(T.m, gi)[q] = acc[q] = mAcc(T.m, gi)[q] + mAcc(T.m, gj)[q];
+    slot_colour(T.m, gi, cm, acc, den, eps_psd);
   }
   mTs(T.m, gi) = fmax(mTs(T.m, gi), mTs(T.m, gj));
   if (T.m.created_timestamps) mCreated(T.m, gi) = fmin(mCreated(T.m, gi), mCreated(T.m, gj));
@@ -350,78 +389,20 @@ GC_DEV void merge_apply_pair(const Tile& T, const double* __restrict__ mu, const
 }
 
 // each selected (disjoint) pair of the tile
-__global__ void k_merge_apply(Tile T, const double* __restrict__ mu, const double* __restrict__ Sig,
+__global__ void k_merge_apply(Tiles S, int64_t a0, const double* __restrict__ mu, const double* __restrict__ Sig,
                               const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel, double eps_psd,
                               int max_pairs) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= max_pairs || k >= *n_sel) return;
-  merge_apply_pair(T, mu, Sig, sel[2 * k], sel[2 * k + 1], eps_psd);
+  const int64_t la = blockIdx.y;
+  if (k >= max_pairs || k >= n_sel[a0 + la]) return;
+  const int32_t* sl = sel + la * 2 * max_pairs;
+  merge_apply_pair(tile_of(S, a0 + la), mu + 3 * la * S.n, Sig + 9 * la * S.n, sl[2 * k], sl[2 * k + 1], eps_psd);
 }
 
-// ---- the batched pass (gc_primitive_map_maintain): the same per-slot bodies over the active tiles,
-// active tile a = the slot range [dense[a] * n, (dense[a] + 1) * n); what the per-tile entries decide
-// on the host is read here from the device statistics (kMmStats doubles per active tile)
-constexpr int kMmStats = GC_MAP_MAINTAIN_STATS_TILE;
-static_assert(kMmStats == 8, "the statistics row is written by index below");
-
-struct Tiles {
-  gc_primitive_map m;
-  int64_t n;
-  const int32_t* dense;
-};
-GC_DEV Tile tile_of(const Tiles& S, int64_t a) { return Tile{S.m, (int64_t)S.dense[a] * S.n, S.n}; }
-GC_DEV bool merge_runs(const double* __restrict__ stats, int64_t a) {
-  return stats[kMmStats * a + 7] == (double)GC_MAP_MAINTAIN_MERGE_RAN;
-}
-
-// k_cull_count with the tile in blockIdx.y and its threshold thr_a[a] (NULL: thr0); partials of tile a at
-// part + a * gridDim.x * 4, blocks and slots in k_cull_count's order. APPLY: the slot is also culled and
-// forgotten (w *= gamma) in the same visit, which no other slot's result depends on.
-template <bool APPLY>
-__global__ void __launch_bounds__(256) k_mm_cull(Tiles S, double thr0, const double* __restrict__ thr_a, double gamma,
-                                                 double* part) {
-  const Tile T = tile_of(S, blockIdx.y);
-  const double thr = thr_a ? thr_a[blockIdx.y] : thr0;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x) {
-    const bool below = cull_count_slot(T, s, thr, acc);
-    if (APPLY) {
-      if (below) mValid(T.m, T.s0 + s) = 0;
-      mW(T.m, T.s0 + s) = gamma * mW(T.m, T.s0 + s);
-    }
-  }
-  block_partials<4>(acc, part + (size_t)blockIdx.y * gridDim.x * 4);
-}
-
-// k_recency with the tile in blockIdx.y (gc_primitive_map_recency_inflate_tiles): the same slots per thread and
-// the same block tree, partials of tile a at part + a * gridDim.x * 3
-__global__ void __launch_bounds__(256) k_mm_recency(Tiles S, int64_t seq, double lam, double min_scale, double* part) {
-  double acc[3] = {0.0, 0.0, 0.0};
-  recency_slots(tile_of(S, blockIdx.y), seq, lam, min_scale, acc);
-  block_partials<3>(acc, part + (size_t)blockIdx.y * gridDim.x * 3);
-}
-
-// k_sum_parts per tile (blockIdx.x): out[a * NV + v]
-template <int NV>
-__global__ void k_mm_sum_parts(const double* __restrict__ part, int blocks, double* out) {
-  if ((int)threadIdx.x >= NV) return;
-  const double* p = part + (size_t)blockIdx.x * blocks * NV;
-  double s = 0.0;
-  for (int b = 0; b < blocks; ++b) s += p[b * NV + threadIdx.x];
-  out[blockIdx.x * NV + threadIdx.x] = s;
-}
-
-// k_cull_keys with the tile in blockIdx.y: keys[a * n + s]
-__global__ void k_mm_cull_keys(Tiles S, double* keys) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= S.n) return;
-  const Tile T = tile_of(S, blockIdx.y);
-  keys[(int64_t)blockIdx.y * S.n + s] = mW(T.m, T.s0 + s) * (mValid(T.m, T.s0 + s) ? 1.0 : 0.0);
-}
-
+// ---- the per-tile decisions of gc_primitive_map_maintain, one thread per active tile
 // primitive_map.py:1222-1229 per tile: sums = the count at thr0, keys = the tile's w·valid descending
-__global__ void k_mm_cull_thr(int n_active, int64_t n, const double* __restrict__ sums,
-                              const double* __restrict__ keys, double thr0, int64_t max_primitives, double* thr_a) {
+__global__ void k_tiles_cull_thr(int n_active, int64_t n, const double* __restrict__ sums,
+                                 const double* __restrict__ keys, double thr0, int64_t max_primitives, double* thr_a) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= n_active) return;
   const double* c = sums + 4 * a;
@@ -430,13 +411,13 @@ __global__ void k_mm_cull_thr(int n_active, int64_t n, const double* __restrict_
 }
 
 // the cull's statistics and the merge's no-op tests (primitive_map.py:1879-1890), the valid count after the cull
-__global__ void k_mm_cull_stats(int n_active, int64_t n, const double* __restrict__ sums,
+__global__ void k_tiles_cull_stats(int n_active, int64_t n, const double* __restrict__ sums,
                                 const double* __restrict__ thr_a, double thr0, int max_pairs, int capped,
                                 double* stats) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= n_active) return;
   const double* c = sums + 4 * a;
-  double* st = stats + kMmStats * a;
+  double* st = stats + kStats * a;
   const double after = c[0] - c[1];
   st[0] = c[0];
   st[1] = c[1];
@@ -450,63 +431,14 @@ __global__ void k_mm_cull_stats(int n_active, int64_t n, const double* __restric
                                                     : (double)GC_MAP_MAINTAIN_MERGE_RAN;
 }
 
-// the group's tiles a0 .. a0 + g - 1, the tile of the group in blockIdx.y; mu / Sig / dets / used hold n
-// slots per tile, keys / vals P pairs
-__global__ void k_mm_merge_prep(Tiles S, int64_t a0, const double* __restrict__ stats, double eps_lift, double* mu,
-                                double* Sig, double* dets) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
-  if (s >= S.n || !merge_runs(stats, a0 + la)) return;
-  merge_prep_slot(tile_of(S, a0 + la), s, eps_lift, mu + 3 * la * S.n, Sig + 9 * la * S.n, dets + la * S.n);
-}
-
-__global__ void k_mm_merge_dist(Tiles S, int64_t a0, int64_t P, const double* __restrict__ stats,
-                                const double* __restrict__ mu, const double* __restrict__ Sig,
-                                const double* __restrict__ dets, double eps_lift, double* keys, uint32_t* vals) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, la = blockIdx.y;
-  if (p >= P) return;
-  const int64_t x = la * P + p;
-  vals[x] = (uint32_t)p;
-  keys[x] = merge_runs(stats, a0 + la) ? merge_pair_dist(tile_of(S, a0 + la), p, mu + 3 * la * S.n,
-                                                         Sig + 9 * la * S.n, dets + la * S.n, eps_lift)
-                                       : INFINITY;
-}
-
-// one workgroup per tile of the group, one lane walking (k_merge_select)
-__global__ void k_mm_merge_select(int64_t n, int64_t a0, int64_t P, const double* __restrict__ stats,
-                                  const double* __restrict__ keys, const uint32_t* __restrict__ vals, double thr,
-                                  int max_pairs, uint8_t* used, int32_t* sel, int32_t* n_sel) {
-  const int64_t la = blockIdx.x;
-  if (threadIdx.x != 0 || !merge_runs(stats, a0 + la)) return;
-  n_sel[a0 + la] = merge_select_walk(n, P, keys + la * P, vals + la * P, thr, max_pairs, used + la * n,
-                                     sel + la * 2 * max_pairs);
-}
-
-__global__ void k_mm_merge_apply(Tiles S, int64_t a0, const double* __restrict__ mu, const double* __restrict__ Sig,
-                                 const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel, double eps_psd,
-                                 int max_pairs) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t la = blockIdx.y;
-  if (k >= max_pairs || k >= n_sel[a0 + la]) return;
-  const int32_t* sl = sel + la * 2 * max_pairs;
-  merge_apply_pair(tile_of(S, a0 + la), mu + 3 * la * S.n, Sig + 9 * la * S.n, sl[2 * k], sl[2 * k + 1], eps_psd);
-}
-
-__global__ void __launch_bounds__(256) k_mm_count_valid(Tiles S, double* part) {
-  const Tile T = tile_of(S, blockIdx.y);
-  double acc[1] = {0.0};
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T.n; s += (int64_t)gridDim.x * blockDim.x)
-    acc[0] += mValid(T.m, T.s0 + s) ? 1.0 : 0.0;
-  block_partials<1>(acc, part + (size_t)blockIdx.y * gridDim.x);
-}
-
-__global__ void k_mm_merge_stats(int n_active, const double* __restrict__ part, int blocks,
+__global__ void k_tiles_merge_stats(int n_active, const double* __restrict__ part, int blocks,
                                  const int32_t* __restrict__ n_sel, double* stats) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= n_active) return;
   double s = 0.0;
   for (int b = 0; b < blocks; ++b) s += part[(size_t)a * blocks + b];
-  stats[kMmStats * a + 5] = (double)n_sel[a];
-  stats[kMmStats * a + 6] = s;
+  stats[kStats * a + 5] = (double)n_sel[a];
+  stats[kStats * a + 6] = s;
 }
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -515,13 +447,73 @@ unsigned part_blocks(int64_t n) {
   return (unsigned)(b < kPartBlocks ? (b > 0 ? b : 1) : kPartBlocks);
 }
 
-// reduction pass: launch KER over the tile into part, then fixed-order finish into out (device)
+// reduction pass over n_tiles tiles of n slots: launch(grid) writes part_blocks(n) x NV partials per tile into
+// part, then the fixed-order finish into out[a * NV + v] (device)
 template <int NV, typename Launch>
-int reduce_into(gc_ctx* ctx, int64_t n, double* part, double* out, Launch launch) {
+int reduce_into(gc_ctx* ctx, int64_t n, int64_t n_tiles, double* part, double* out, Launch launch) {
   const unsigned nb = part_blocks(n);
-  launch(nb);
+  launch(dim3(nb, (unsigned)n_tiles));
   GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_sum_parts<NV>, dim3(1), dim3(64), 0, ctx->stream, part, (int)nb, out);
+  hipLaunchKernelGGL(k_sum_parts<NV>, dim3((unsigned)n_tiles), dim3(64), 0, ctx->stream, (const double*)part, (int)nb,
+                     out);
+  GC_LAUNCH_CHECK(ctx);
+  return GC_OK;
+}
+
+// radix_sort_pairs on the context's stream, a failure reported as the context's error
+int sort_pairs(gc_ctx* ctx, const double* keys_in, double* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
+               int64_t n_seg, int64_t len, bool descending, void* tmp) {
+  if (gc::radix_sort_pairs(ctx->stream, keys_in, keys_out, vals_in, vals_out, n_seg, len, descending, tmp) !=
+      hipSuccess) {
+    gc::set_error(ctx, "radix sort failed");
+    return GC_ERR_RUNTIME;
+  }
+  return GC_OK;
+}
+
+// scratch of a merge over a group of G tiles of n slots (P pairs each); n_sel is the caller's
+struct MergeScratch {
+  double *mu, *Sig, *dets, *keys_in, *keys;
+  uint32_t *vals_in, *vals;
+  uint8_t* used;
+  int32_t* sel;
+  void* tmp;
+};
+MergeScratch merge_layout(Carver& c, int64_t G, int64_t n, int64_t P, int max_pairs) {
+  MergeScratch s;
+  s.mu = c.take<double>(3 * (size_t)(G * n));
+  s.Sig = c.take<double>(9 * (size_t)(G * n));
+  s.dets = c.take<double>((size_t)(G * n));
+  s.keys_in = c.take<double>((size_t)(G * P));
+  s.keys = c.take<double>((size_t)(G * P));
+  s.vals_in = c.take<uint32_t>((size_t)(G * P));
+  s.vals = c.take<uint32_t>((size_t)(G * P));
+  s.used = c.take<uint8_t>((size_t)(G * n));
+  s.sel = c.take<int32_t>(2 * (size_t)G * (size_t)std::max(max_pairs, 1));
+  s.tmp = c.take<char>(P > 0 ? gc::sort_temp_bytes(G, P, true) : 0);
+  return s;
+}
+
+// The merge-reduce of the g tiles a0 .. a0 + g - 1 of the span (n >= 2 slots each, max_pairs >= 1), no host
+// wait: distances, one segmented sort, the greedy selection and the merges; n_sel[a] = the pairs merged in
+// tile a (written only where the merge runs, merge_runs).
+int merge_group(gc_ctx* ctx, const Tiles& S, int64_t a0, int64_t g, const double* d_stats, const MergeScratch& s,
+                double merge_thr, int max_pairs, double eps_psd, double eps_lift, int32_t* n_sel) {
+  const int64_t P = S.n * (S.n - 1) / 2;
+  GC_HIP(ctx, hipMemsetAsync(s.used, 0, (size_t)(g * S.n), ctx->stream));
+  hipLaunchKernelGGL(k_merge_prep, dim3(blocks_for(S.n), (unsigned)g), dim3(256), 0, ctx->stream, S, a0, d_stats,
+                     eps_lift, s.mu, s.Sig, s.dets);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_merge_dist, dim3(blocks_for(P), (unsigned)g), dim3(256), 0, ctx->stream, S, a0, P, d_stats,
+                     (const double*)s.mu, (const double*)s.Sig, (const double*)s.dets, eps_lift, s.keys_in, s.vals_in);
+  GC_LAUNCH_CHECK(ctx);
+  if (int rc = sort_pairs(ctx, s.keys_in, s.keys, s.vals_in, s.vals, g, P, false, s.tmp)) return rc;
+  hipLaunchKernelGGL(k_merge_select, dim3((unsigned)g), dim3(64), 0, ctx->stream, S.n, a0, P, d_stats,
+                     (const double*)s.keys, (const uint32_t*)s.vals, merge_thr, max_pairs, s.used, s.sel, n_sel);
+  GC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(k_merge_apply, dim3((unsigned)((max_pairs + 255) / 256), (unsigned)g), dim3(256), 0, ctx->stream,
+                     S, a0, (const double*)s.mu, (const double*)s.Sig, (const int32_t*)s.sel, (const int32_t*)n_sel,
+                     eps_psd, max_pairs);
   GC_LAUNCH_CHECK(ctx);
   return GC_OK;
 }
@@ -572,13 +564,9 @@ int check_active_tiles(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile,
 
 }  // namespace
 
-int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid) {
-  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
-  if (int rc_j = gc::join_side(ctx)) return rc_j;  // a pipeline's in-scan update may still write the map
-  GC_CHECK_ARG(ctx, map != nullptr, "NULL map");
-  GC_CHECK_ARG(ctx, map->m_slots > 0 && slot0 >= 0 && n_slots >= 0 && slot0 + n_slots <= map->m_slots,
-               "tile range outside the map");
-  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMaxLobesOps, "n_lobes must be in [1, 8]");
+int check_map_core(gc_ctx* ctx, const gc_primitive_map* map, int64_t max_slots, bool need_valid) {
+  GC_CHECK_ARG(ctx, map->m_slots > 0 && map->m_slots < max_slots, "m_slots out of range");
+  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
   {
     const char* lay_ = gc::map_layout_error(*map);
     GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
@@ -587,10 +575,24 @@ int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t 
                         map->last_supported_scan_seq && map->last_update_scan_seq,
                "NULL map field");
   GC_CHECK_ARG(ctx, !need_valid || map->valid_mask, "valid_mask is required");
+  return GC_OK;
+}
+
+int check_map(gc_ctx* ctx, const gc_primitive_map* map, int64_t max_slots, bool need_valid) {
+  if (int rc = check_map_core(ctx, map, max_slots, need_valid)) return rc;
   const bool color = map->cam_mass != nullptr;
   GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
                "colour fields must be all set or all NULL");
   return GC_OK;
+}
+
+int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid) {
+  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
+  if (int rc_j = gc::join_side(ctx)) return rc_j;  // a pipeline's in-scan update may still write the map
+  GC_CHECK_ARG(ctx, map != nullptr, "NULL map");
+  GC_CHECK_ARG(ctx, map->m_slots > 0 && slot0 >= 0 && n_slots >= 0 && slot0 + n_slots <= map->m_slots,
+               "tile range outside the map");
+  return check_map(ctx, map, INT64_MAX, need_valid);
 }
 
 size_t insert_scratch_bytes(int64_t n_slots) {
@@ -612,19 +614,15 @@ int insert_launch(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64
   hipLaunchKernelGGL(k_insert_keys, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, scan_seq,
                      recency_decay_lambda, s.keys_in, s.vals_in);
   GC_LAUNCH_CHECK(ctx);
-  if (gc::radix_sort_pairs(ctx->stream, s.keys_in, s.keys, (const uint32_t*)s.vals_in, (uint32_t*)s.vals, 1, n_slots,
-                           false, s.tmp) != hipSuccess) {
-    gc::set_error(ctx, "radix sort failed");
-    return GC_ERR_RUNTIME;
-  }
+  if (int rc = sort_pairs(ctx, s.keys_in, s.keys, (const uint32_t*)s.vals_in, (uint32_t*)s.vals, 1, n_slots, false,
+                          s.tmp))
+    return rc;
   hipLaunchKernelGGL(k_insert_apply, dim3(1), dim3(256), 0, ctx->stream, T, *batch, (const int32_t*)s.vals, timestamp,
                      scan_seq, next_global_id, d_id_offset, d_target_slots_out, d_new_ids_out, d_out2 + 1);
   GC_LAUNCH_CHECK(ctx);
-  if (int rc = reduce_into<1>(ctx, n_slots, s.part, d_out2, [&](unsigned nb) {
-        hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, s.part);
-      }))
-    return rc;
-  return GC_OK;
+  return reduce_into<1>(ctx, n_slots, 1, s.part, d_out2, [&](dim3 grid) {
+    hipLaunchKernelGGL(k_count_valid, grid, dim3(256), 0, ctx->stream, Tiles{*map, slot0, n_slots, nullptr}, s.part);
+  });
 }
 }  // namespace gc
 
@@ -654,10 +652,9 @@ int32_t gc_primitive_map_recency_inflate(gc_ctx* ctx, const gc_primitive_map* ma
         out = c.take<double>(3);
       }))
     return rc;
-  const Tile T{*map, slot0, n_slots};
-  if (int rc = reduce_into<3>(ctx, n_slots, part, out, [&](unsigned nb) {
-        hipLaunchKernelGGL(k_recency, dim3(nb), dim3(256), 0, ctx->stream, T, scan_seq, decay_lambda, min_scale,
-                           part);
+  const Tiles S{*map, slot0, n_slots, nullptr};
+  if (int rc = reduce_into<3>(ctx, n_slots, 1, part, out, [&](dim3 grid) {
+        hipLaunchKernelGGL(k_recency, grid, dim3(256), 0, ctx->stream, S, scan_seq, decay_lambda, min_scale, part);
       }))
     return rc;
   return h_stats3 ? download(ctx, h_stats3, out, 3 * sizeof(double)) : GC_OK;
@@ -671,17 +668,14 @@ int32_t gc_primitive_map_recency_inflate_tiles(gc_ctx* ctx, const gc_primitive_m
   if (int rc = check_active_tiles(ctx, map, m_tile, n_active, d_active_dense, h_active_dense)) return rc;
   if (n_active == 0) return GC_OK;
   GC_CHECK_ARG(ctx, d_stats != nullptr, "d_stats is NULL");
-  const unsigned nb = part_blocks(m_tile);  // the per-tile entry's partition of a tile of m_tile slots
   double* part;
-  if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) { part = c.take<double>(3 * (size_t)nb * n_active); }))
+  if (int rc = gc::carve_scratch(
+          ctx, [&](gc::Carver& c) { part = c.take<double>(3 * (size_t)part_blocks(m_tile) * n_active); }))
     return rc;
-  hipLaunchKernelGGL(k_mm_recency, dim3(nb, (unsigned)n_active), dim3(256), 0, ctx->stream,
-                     Tiles{*map, m_tile, d_active_dense}, scan_seq, decay_lambda, min_scale, part);
-  GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_mm_sum_parts<3>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
-                     (int)nb, d_stats);
-  GC_LAUNCH_CHECK(ctx);
-  return GC_OK;
+  const Tiles S{*map, 0, m_tile, d_active_dense};
+  return reduce_into<3>(ctx, m_tile, n_active, part, d_stats, [&](dim3 grid) {
+    hipLaunchKernelGGL(k_recency, grid, dim3(256), 0, ctx->stream, S, scan_seq, decay_lambda, min_scale, part);
+  });
 }
 
 int32_t gc_test_radix_sort(gc_ctx* ctx, const double* d_keys_in, const uint32_t* d_vals_in, int64_t n_seg, int64_t L,
@@ -714,10 +708,11 @@ int32_t gc_primitive_map_cull(gc_ctx* ctx, const gc_primitive_map* map, int64_t 
         tmp = c.take<char>(gc::sort_temp_bytes(1, n_slots, false));
       }))
     return rc;
-  const Tile T{*map, slot0, n_slots};
+  const Tiles S{*map, slot0, n_slots, nullptr};
+  const double* no_thr = nullptr;
   auto count = [&](double thr, double* h4) -> int {
-    if (int rc = reduce_into<4>(ctx, n_slots, part, out, [&](unsigned nb) {
-          hipLaunchKernelGGL(k_cull_count, dim3(nb), dim3(256), 0, ctx->stream, T, thr, part);
+    if (int rc = reduce_into<4>(ctx, n_slots, 1, part, out, [&](dim3 grid) {
+          hipLaunchKernelGGL((k_cull<false, false>), grid, dim3(256), 0, ctx->stream, S, thr, no_thr, 1.0, part);
         }))
       return rc;
     return download(ctx, h4, out, 4 * sizeof(double));
@@ -728,17 +723,15 @@ int32_t gc_primitive_map_cull(gc_ctx* ctx, const gc_primitive_map* map, int64_t 
   double thr = weight_threshold;
   // primitive_map.py:1222-1229: keep the top max_primitives by weight
   if (max_primitives >= 0 && n_valid - c[1] > (double)max_primitives && max_primitives < n_slots) {
-    hipLaunchKernelGGL(k_cull_keys, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, keys_in);
+    hipLaunchKernelGGL(k_cull_keys, dim3(blocks_for(n_slots), 1), dim3(256), 0, ctx->stream, S, keys_in);
     GC_LAUNCH_CHECK(ctx);
-    if (gc::radix_sort_pairs(ctx->stream, keys_in, keys, nullptr, nullptr, 1, n_slots, true, tmp) != hipSuccess) {
-      gc::set_error(ctx, "radix sort failed");
-      return GC_ERR_RUNTIME;
-    }
+    if (int rc = sort_pairs(ctx, keys_in, keys, nullptr, nullptr, 1, n_slots, true, tmp)) return rc;
     if (int rc = download(ctx, &thr, keys + max_primitives, sizeof(double))) return rc;
     if (int rc = count(thr, c)) return rc;
   }
-  if (c[1] > 0.0) {
-    hipLaunchKernelGGL(k_cull_apply, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, thr);
+  if (c[1] > 0.0) {  // the cull alone (the forgetting is gc_primitive_map_forget's); its recount in part is not read
+    hipLaunchKernelGGL((k_cull<true, false>), dim3(part_blocks(n_slots), 1), dim3(256), 0, ctx->stream, S, thr, no_thr,
+                       1.0, part);
     GC_LAUNCH_CHECK(ctx);
   }
   h_out4[0] = c[1];
@@ -780,31 +773,21 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
   GC_CHECK_ARG(ctx, n_slots <= 65536, "merge-reduce tile larger than 65536 slots");
   h_out2[0] = 0;
   h_out2[1] = 0;
-  const Tile T{*map, slot0, n_slots};
+  const Tiles S{*map, slot0, n_slots, nullptr};
   const int64_t P = n_slots * (n_slots - 1) / 2;
-  double *part, *out, *mu, *Sig, *dets, *keys_in, *keys;
-  uint32_t *vals_in, *vals;
-  uint8_t* used;
-  int32_t* sel;  // max_pairs pairs, then their count
-  void* tmp;
+  double *part, *out;
+  int32_t* n_sel;
+  MergeScratch mg;
   if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
         part = c.take<double>(kPartBlocks);
         out = c.take<double>(1);
-        mu = c.take<double>(3 * (size_t)n_slots);
-        Sig = c.take<double>(9 * (size_t)n_slots);
-        dets = c.take<double>(n_slots);
-        keys_in = c.take<double>(P);
-        keys = c.take<double>(P);
-        vals_in = c.take<uint32_t>(P);
-        vals = c.take<uint32_t>(P);
-        used = c.take<uint8_t>(n_slots);
-        sel = c.take<int32_t>(2 * (size_t)(max_pairs > 0 ? max_pairs : 1) + 1);
-        tmp = c.take<char>(P > 0 ? gc::sort_temp_bytes(1, P, true) : 0);
+        n_sel = c.take<int32_t>(1);
+        mg = merge_layout(c, 1, n_slots, P, max_pairs);
       }))
     return rc;
   auto count_valid = [&](double* h) -> int {
-    if (int rc = reduce_into<1>(ctx, n_slots, part, out, [&](unsigned nb) {
-          hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(256), 0, ctx->stream, T, part);
+    if (int rc = reduce_into<1>(ctx, n_slots, 1, part, out, [&](dim3 grid) {
+          hipLaunchKernelGGL(k_count_valid, grid, dim3(256), 0, ctx->stream, S, part);
         }))
       return rc;
     return download(ctx, h, out, sizeof(double));
@@ -814,24 +797,9 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
     if (int rc = count_valid(&nv)) return rc;
   h_out2[1] = (int64_t)nv;
   if (n_slots < 2 || nv < 2.0 || max_pairs <= 0) return GC_OK;  // primitive_map.py:1879-1880
-  int32_t* n_sel = sel + 2 * max_pairs;
-  GC_HIP(ctx, hipMemsetAsync(used, 0, (size_t)n_slots, ctx->stream));
-  hipLaunchKernelGGL(k_merge_prep, dim3(blocks_for(n_slots)), dim3(256), 0, ctx->stream, T, eps_lift, mu, Sig, dets);
-  GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_merge_dist, dim3(blocks_for(P)), dim3(256), 0, ctx->stream, T, P, (const double*)mu,
-                     (const double*)Sig, (const double*)dets, eps_lift, keys_in, vals_in);
-  GC_LAUNCH_CHECK(ctx);
-  if (gc::radix_sort_pairs(ctx->stream, keys_in, keys, vals_in, vals, 1, P, false, tmp) != hipSuccess) {
-    gc::set_error(ctx, "radix sort failed");
-    return GC_ERR_RUNTIME;
-  }
-  hipLaunchKernelGGL(k_merge_select, dim3(1), dim3(64), 0, ctx->stream, n_slots, P, (const double*)keys,
-                     (const uint32_t*)vals, merge_threshold, (int)max_pairs, used, sel, n_sel);
-  GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_merge_apply, dim3((unsigned)((max_pairs + 255) / 256)), dim3(256), 0, ctx->stream, T,
-                     (const double*)mu, (const double*)Sig, (const int32_t*)sel, (const int32_t*)n_sel, eps_psd,
-                     (int)max_pairs);
-  GC_LAUNCH_CHECK(ctx);
+  // decided here on the host: no statistics row, the merge runs
+  if (int rc = merge_group(ctx, S, 0, 1, nullptr, mg, merge_threshold, (int)max_pairs, eps_psd, eps_lift, n_sel))
+    return rc;
   int32_t ns = 0;
   if (int rc = download(ctx, &ns, n_sel, sizeof(ns))) return rc;
   if (int rc = count_valid(&nv)) return rc;
@@ -864,46 +832,26 @@ int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int6
                                              ((int64_t)1 << 32) - 1);
     G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(budget / P, kMaintainGroupTiles), n_active));
   }
-  const unsigned nb = part_blocks(m_tile);
-
   // one scratch for the whole call, sized before the first launch (growing it waits for the stream): the
   // partials, sums and thresholds, then the cull's sort and the merge's group, used one after the other
   struct CullSort {
     double *keys_in, *keys;
     void* tmp;
   } cs{};
-  struct MergeGroup {
-    double *mu, *Sig, *dets, *keys_in, *keys;
-    uint32_t *vals_in, *vals;
-    uint8_t* used;
-    int32_t* sel;
-    void* tmp;
-  } mg{};
+  MergeScratch mg{};
   auto cull_layout = [&](gc::Carver& c) {
     cs.keys_in = c.take<double>((size_t)slots);
     cs.keys = c.take<double>((size_t)slots);
     cs.tmp = c.take<char>(gc::sort_temp_bytes(n_active, m_tile, false));
   };
-  auto merge_layout = [&](gc::Carver& c) {
-    mg.mu = c.take<double>(3 * (size_t)(G * m_tile));
-    mg.Sig = c.take<double>(9 * (size_t)(G * m_tile));
-    mg.dets = c.take<double>((size_t)(G * m_tile));
-    mg.keys_in = c.take<double>((size_t)(G * P));
-    mg.keys = c.take<double>((size_t)(G * P));
-    mg.vals_in = c.take<uint32_t>((size_t)(G * P));
-    mg.vals = c.take<uint32_t>((size_t)(G * P));
-    mg.used = c.take<uint8_t>((size_t)(G * m_tile));
-    mg.sel = c.take<int32_t>(2 * (size_t)G * (size_t)max_pairs);
-    mg.tmp = c.take<char>(gc::sort_temp_bytes(G, P, true));
-  };
   gc::Carver cull_size, merge_size;
   if (top) cull_layout(cull_size);
-  if (merge) merge_layout(merge_size);
+  if (merge) merge_layout(merge_size, G, m_tile, P, max_pairs);
   double *part, *sums, *thr_a;
   int32_t* n_sel;
   char* sub;
   if (int rc = gc::carve_scratch(ctx, [&](gc::Carver& c) {
-        part = c.take<double>(4 * (size_t)nb * n_active);
+        part = c.take<double>(4 * (size_t)part_blocks(m_tile) * n_active);
         sums = c.take<double>(4 * (size_t)n_active);
         thr_a = c.take<double>(n_active);
         n_sel = c.take<int32_t>(n_active);
@@ -916,72 +864,46 @@ int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int6
   }
   if (merge) {
     gc::Carver c{sub};
-    merge_layout(c);
+    mg = merge_layout(c, G, m_tile, P, max_pairs);
   }
 
   // ---- the first launch; no host wait from here on
-  const Tiles S{*map, m_tile, d_active_dense};
-  const dim3 tile_grid(nb, (unsigned)n_active), per_tile(blocks_for(n_active));
+  const Tiles S{*map, 0, m_tile, d_active_dense};
+  const dim3 per_tile(blocks_for(n_active));
   const double* thr_dev = nullptr;
-  if (top) {  // the launches are host-known, the branch is each tile's own (k_mm_cull_thr)
-    hipLaunchKernelGGL(k_mm_cull<false>, tile_grid, dim3(256), 0, ctx->stream, S, thr0, (const double*)nullptr, gamma,
-                       part);
-    GC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mm_sum_parts<4>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
-                       (int)nb, sums);
-    GC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mm_cull_keys, dim3(blocks_for(m_tile), (unsigned)n_active), dim3(256), 0, ctx->stream, S,
+  if (top) {  // the launches are host-known, the branch is each tile's own (k_tiles_cull_thr)
+    if (int rc = reduce_into<4>(ctx, m_tile, n_active, part, sums, [&](dim3 grid) {
+          hipLaunchKernelGGL((k_cull<false, false>), grid, dim3(256), 0, ctx->stream, S, thr0, thr_dev, gamma, part);
+        }))
+      return rc;
+    hipLaunchKernelGGL(k_cull_keys, dim3(blocks_for(m_tile), (unsigned)n_active), dim3(256), 0, ctx->stream, S,
                        cs.keys_in);
     GC_LAUNCH_CHECK(ctx);
-    if (gc::radix_sort_pairs(ctx->stream, cs.keys_in, cs.keys, nullptr, nullptr, n_active, m_tile, true, cs.tmp) !=
-        hipSuccess) {
-      gc::set_error(ctx, "radix sort failed");
-      return GC_ERR_RUNTIME;
-    }
-    hipLaunchKernelGGL(k_mm_cull_thr, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile, (const double*)sums,
-                       (const double*)cs.keys, thr0, max_primitives, thr_a);
+    if (int rc = sort_pairs(ctx, cs.keys_in, cs.keys, nullptr, nullptr, n_active, m_tile, true, cs.tmp)) return rc;
+    hipLaunchKernelGGL(k_tiles_cull_thr, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile,
+                       (const double*)sums, (const double*)cs.keys, thr0, max_primitives, thr_a);
     GC_LAUNCH_CHECK(ctx);
     thr_dev = thr_a;
   }
   // count at the tile's threshold, cull and forget in one streaming visit
-  hipLaunchKernelGGL(k_mm_cull<true>, tile_grid, dim3(256), 0, ctx->stream, S, thr0, thr_dev, gamma, part);
-  GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_mm_sum_parts<4>, dim3((unsigned)n_active), dim3(64), 0, ctx->stream, (const double*)part,
-                     (int)nb, sums);
-  GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_mm_cull_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile, (const double*)sums,
-                     thr_dev, thr0, (int)max_pairs, capped ? 1 : 0, d_stats);
+  if (int rc = reduce_into<4>(ctx, m_tile, n_active, part, sums, [&](dim3 grid) {
+        hipLaunchKernelGGL((k_cull<true, true>), grid, dim3(256), 0, ctx->stream, S, thr0, thr_dev, gamma, part);
+      }))
+    return rc;
+  hipLaunchKernelGGL(k_tiles_cull_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, m_tile,
+                     (const double*)sums, thr_dev, thr0, (int)max_pairs, capped ? 1 : 0, d_stats);
   GC_LAUNCH_CHECK(ctx);
   if (!merge) return GC_OK;
 
   GC_HIP(ctx, hipMemsetAsync(n_sel, 0, sizeof(int32_t) * (size_t)n_active, ctx->stream));
-  for (int64_t a0 = 0; a0 < n_active; a0 += G) {
-    const int64_t g = std::min<int64_t>(G, n_active - a0), gs = g * m_tile;
-    GC_HIP(ctx, hipMemsetAsync(mg.used, 0, (size_t)gs, ctx->stream));
-    hipLaunchKernelGGL(k_mm_merge_prep, dim3(blocks_for(m_tile), (unsigned)g), dim3(256), 0, ctx->stream, S, a0,
-                       (const double*)d_stats, eps_lift, mg.mu, mg.Sig, mg.dets);
-    GC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mm_merge_dist, dim3(blocks_for(P), (unsigned)g), dim3(256), 0, ctx->stream, S, a0, P,
-                       (const double*)d_stats, (const double*)mg.mu, (const double*)mg.Sig, (const double*)mg.dets,
-                       eps_lift, mg.keys_in, mg.vals_in);
-    GC_LAUNCH_CHECK(ctx);
-    if (gc::radix_sort_pairs(ctx->stream, mg.keys_in, mg.keys, mg.vals_in, mg.vals, g, P, false, mg.tmp) !=
-        hipSuccess) {
-      gc::set_error(ctx, "radix sort failed");
-      return GC_ERR_RUNTIME;
-    }
-    hipLaunchKernelGGL(k_mm_merge_select, dim3((unsigned)g), dim3(64), 0, ctx->stream, m_tile, a0, P,
-                       (const double*)d_stats, (const double*)mg.keys, (const uint32_t*)mg.vals, merge_thr,
-                       (int)max_pairs, mg.used, mg.sel, n_sel);
-    GC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mm_merge_apply, dim3((unsigned)((max_pairs + 255) / 256), (unsigned)g), dim3(256), 0,
-                       ctx->stream, S, a0, (const double*)mg.mu, (const double*)mg.Sig, (const int32_t*)mg.sel,
-                       (const int32_t*)n_sel, eps_psd, (int)max_pairs);
-    GC_LAUNCH_CHECK(ctx);
-  }
-  hipLaunchKernelGGL(k_mm_count_valid, tile_grid, dim3(256), 0, ctx->stream, S, part);
+  for (int64_t a0 = 0; a0 < n_active; a0 += G)
+    if (int rc = merge_group(ctx, S, a0, std::min<int64_t>(G, n_active - a0), d_stats, mg, merge_thr, (int)max_pairs,
+                             eps_psd, eps_lift, n_sel))
+      return rc;
+  const unsigned nb = part_blocks(m_tile);
+  hipLaunchKernelGGL(k_count_valid, dim3(nb, (unsigned)n_active), dim3(256), 0, ctx->stream, S, part);
   GC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(k_mm_merge_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, (const double*)part,
+  hipLaunchKernelGGL(k_tiles_merge_stats, per_tile, dim3(256), 0, ctx->stream, (int)n_active, (const double*)part,
                      (int)nb, (const int32_t*)n_sel, d_stats);
   GC_LAUNCH_CHECK(ctx);
   return GC_OK;

@@ -1,11 +1,15 @@
 // gc_mapslot.h — slot addressing of a gc_primitive_map in either device layout (include/gcslam.h):
-// the reference's per-field arrays (slot_bytes = 0) or one packed record per slot.
+// the reference's per-field arrays (slot_bytes = 0) or one packed record per slot, and the rules every
+// map operator shares: the lobe bound, the field list, a slot's colour estimate, the tile key.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/gcslam.h"
+#include "gc_math.h"
 
 namespace gc {
+
+constexpr int kMapMaxLobes = 8;  // vMF lobes per primitive that the kernels hold in registers
 
 // slot s of a field of `width` elements
 template <class T>
@@ -76,6 +80,14 @@ inline void map_record_layout(int n_lobes, int64_t* off, int64_t* slot_bytes) {
   *slot_bytes = up128(b2 + 81);
 }
 
+// the map's field pointers in the order of map_record_layout's offsets
+inline void map_fields(const gc_primitive_map& m, const void* (&f)[kRecFields]) {
+  const void* p[kRecFields] = {m.Lambdas, m.thetas, m.etas, m.weights, m.timestamps, m.last_supported_scan_seq,
+                               m.last_update_scan_seq, m.cam_mass, m.lidar_mass, m.rgb_cam_accum, m.rgb_cam_denom,
+                               m.rgb, m.colors, m.valid_mask, m.created_timestamps, m.primitive_ids};
+  for (int k = 0; k < kRecFields; ++k) f[k] = p[k];
+}
+
 // Host check of a map's layout before any kernel dereferences it: per-field arrays (slot_bytes 0),
 // or exactly the packed record of map_record_layout(n_lobes) with every non-NULL field inside the
 // record that Lambdas starts (a shorter slot_bytes would let a fuse write into the next slot's
@@ -87,9 +99,8 @@ inline const char* map_layout_error(const gc_primitive_map& m) {
   if (m.slot_bytes != sb) return "slot_bytes must be 0 (per-field arrays) or gc_primitive_map_record_layout(n_lobes)";
   if (!m.Lambdas) return "NULL Lambdas";
   const char* b0 = (const char*)m.Lambdas;
-  const void* f[kRecFields] = {m.Lambdas, m.thetas, m.etas, m.weights, m.timestamps, m.last_supported_scan_seq,
-                               m.last_update_scan_seq, m.cam_mass, m.lidar_mass, m.rgb_cam_accum, m.rgb_cam_denom,
-                               m.rgb, m.colors, m.valid_mask, m.created_timestamps, m.primitive_ids};
+  const void* f[kRecFields];
+  map_fields(m, f);
   const int64_t width[kRecFields] = {72, 24, 24 * (int64_t)m.n_lobes, 8, 8, 8, 8, 8, 8, 24, 8, 24, 24, 1, 8, 8};
   for (int k = 0; k < kRecFields; ++k) {
     if (!f[k]) continue;
@@ -97,6 +108,32 @@ inline const char* map_layout_error(const gc_primitive_map& m) {
     if (d < 0 || d + width[k] > sb) return "a packed field pointer lies outside its slot record";
   }
   return nullptr;
+}
+
+// A slot's colour estimate from its camera accumulators (primitive_map.py:1090-1105): clip(accum /
+// max(denom, ε), 0, 1) where cam_mass > 0, else gray. The caller chooses ε (the fuse eps_mass, the merge
+// eps_psd).
+GC_DEV void slot_colour_value(double cam, const double* acc, double denom, double eps, double (&v)[3]) {
+  const bool on = cam > 0.0;
+  const double den = fmax(denom, eps);
+  for (int q = 0; q < 3; ++q) v[q] = on ? clampd(acc[q] / den, 0.0, 1.0) : 0.5;
+}
+// the estimate stored as slot s's rgb; colors = rgb
+GC_DEV void slot_colour(const gc_primitive_map& m, int64_t s, double cam, const double* acc, double denom,
+                        double eps) {
+  double v[3];
+  slot_colour_value(cam, acc, denom, eps, v);
+  for (int q = 0; q < 3; ++q) {
+    mRgb(m, s)[q] = v[q];
+    if (m.colors) mCol(m, s)[q] = v[q];
+  }
+}
+
+// the packed key of the tile with hex cell (c1, c2) in slab cz (tile_ids_from_xyz_batch_jax, common/tiling.py:
+// 126-145): each index biased by 2^20 and masked to 21 bits. The cell indices are the caller's (floor(s / h)).
+GC_DEV int64_t pack_tile(int64_t c1, int64_t c2, int64_t cz) {
+  constexpr int64_t b = 1 << 20, m = (1 << 21) - 1;
+  return (((c1 + b) & m) << 42) | (((c2 + b) & m) << 21) | ((cz + b) & m);
 }
 
 }  // namespace gc

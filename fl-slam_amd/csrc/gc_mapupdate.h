@@ -13,8 +13,15 @@ int fuse_launch(gc_ctx* ctx, const gc_primitive_map* map, const gc_fuse_batch* m
                 double eps_lift, double eps_mass, double timestamp, int64_t scan_seq, void* scr,
                 uint32_t** d_counts, unsigned* n_counts);
 
-// The argument check every per-tile entry starts with (gc_mapops.hip; also gc_maptiles.hip): joins the
-// context's side stream, then the tile range, the lobe count, the layout and the field pointers.
+// "Is this gc_primitive_map sound" for every entry that takes one (gc_mapops.hip): 0 < m_slots < max_slots,
+// the lobe count, the layout, the seven core fields, valid_mask where the entry needs it, and the colour
+// fields all set or all NULL. check_map_core stops before the colour fields, for the pipeline's attach, which
+// takes some of them as optional.
+int check_map_core(gc_ctx* ctx, const gc_primitive_map* map, int64_t max_slots, bool need_valid);
+int check_map(gc_ctx* ctx, const gc_primitive_map* map, int64_t max_slots, bool need_valid);
+
+// The argument check every per-tile entry starts with (also gc_maptiles.hip): joins the context's side
+// stream, then the tile range and check_map.
 int check_tile(gc_ctx* ctx, const gc_primitive_map* map, int64_t slot0, int64_t n_slots, bool need_valid);
 
 size_t insert_scratch_bytes(int64_t n_slots);

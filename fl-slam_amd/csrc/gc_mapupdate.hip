@@ -38,7 +38,6 @@ namespace gc {
 namespace {
 
 constexpr int kMuWG = 256;
-constexpr int kMuMaxLobes = 8;
 // the plan kernel's LDS: 13 B per measurement row (score, row index, in_tile) and 13 B per insert
 // proposal (row index, weight, mask) must fit one workgroup's share of the CU's 160 KiB
 constexpr int64_t kMuMaxRows = GC_MAP_UPDATE_MAX_ROWS;
@@ -97,18 +96,6 @@ __global__ void __launch_bounds__(kMuWG) k_mu_expand(MuArgs A, int32_t* slots, d
   mass[r] = (a >= 0 && valid) ? wi * ri : 0.0;  // pipeline.py:1306-1308
 }
 
-// rgb / colors of one slot from its camera accumulators (primitive_map.py:1097-1105)
-GC_DEV void mu_slot_colour(const gc_primitive_map& m, int64_t s, double eps_mass) {
-  const bool on = mCam(m, s) > 0.0;
-  const double den = fmax(mDen(m, s), eps_mass);
-  const double* acc = mAcc(m, s);
-  for (int q = 0; q < 3; ++q) {
-    const double v = on ? clampd(acc[q] / den, 0.0, 1.0) : 0.5;
-    mRgb(m, s)[q] = v;
-    if (m.colors) mCol(m, s)[q] = v;
-  }
-}
-
 __global__ void __launch_bounds__(kMuWG) k_mu_stamp(MuArgs A, const uint8_t* __restrict__ flags,
                                                     unsigned long long* n_distinct) {
   __shared__ unsigned int wg_count;
@@ -121,7 +108,7 @@ __global__ void __launch_bounds__(kMuWG) k_mu_stamp(MuArgs A, const uint8_t* __r
     for (int a = 0; a < A.in.n_active; ++a) {
       const int64_t g = (int64_t)A.in.active_dense[a] * A.in.m_tile + s;
       if (c) mTs(A.map, g) = A.timestamp;
-      if (A.map.cam_mass) mu_slot_colour(A.map, g, A.eps_mass);
+      if (A.map.cam_mass) slot_colour(A.map, g, mCam(A.map, g), mAcc(A.map, g), mDen(A.map, g), A.eps_mass);
     }
   }
   if (c) atomicAdd(&wg_count, c);
@@ -145,26 +132,6 @@ __global__ void __launch_bounds__(kMuWG) k_mu_totals(const double* __restrict__ 
   if (threadIdx.x == 0) {
     stats[0] = red[0];
     stats[1] = (double)*n_distinct;
-  }
-}
-
-// transform_gaussian_to_world (pipeline.py:1248-1256) of one row; Lw / tw / ew may be global memory
-GC_DEV void mu_to_world(const double* R, const double* t, double eps_lift, int L, const double* Lb, const double* tb,
-                        const double* eb, double* Lw, double* tw, double* ew) {
-  double M3[9], Lr[9], Lo[9], mu[3], mw[3], to[3];
-  mat3_mul(R, Lb, M3);
-  mat3_mul_nt(M3, R, Lo);
-  for (int q = 0; q < 9; ++q) Lr[q] = Lb[q] + ((q % 4 == 0) ? eps_lift : 0.0);
-  solve3(Lr, tb, mu);
-  mat3_vec(R, mu, mw);
-  for (int q = 0; q < 3; ++q) mw[q] += t[q];
-  mat3_vec(Lo, mw, to);
-  for (int q = 0; q < 9; ++q) Lw[q] = Lo[q];
-  for (int q = 0; q < 3; ++q) tw[q] = to[q];
-  for (int l = 0; l < L; ++l) {
-    double e[3];
-    mat3_vec(R, eb + 3 * l, e);
-    for (int q = 0; q < 3; ++q) ew[3 * l + q] = e[q];
   }
 }
 
@@ -232,18 +199,15 @@ __global__ void __launch_bounds__(kMuWG) k_mu_plan(MuArgs A, PlanOut P) {
   const int64_t i0 = min<int64_t>((int64_t)t * per, N), i1 = min<int64_t>(i0 + per, N);
   int cnt = 0;
   for (int64_t i = i0; i < i1; ++i) {
-    double Lr[9], mu[3], mw[3];
-    for (int q = 0; q < 9; ++q) Lr[q] = A.in.Lambdas[9 * i + q] + ((q % 4 == 0) ? A.eps_lift : 0.0);
-    solve3(Lr, A.in.thetas + 3 * i, mu);
+    double mu[3], mw[3];
+    prim_mean(A.in.Lambdas + 9 * i, A.in.thetas + 3 * i, A.eps_lift, mu);
     mat3_vec(Rt, mu, mw);
     for (int q = 0; q < 3; ++q) mw[q] += A.pose[q];
-    // tile_ids_from_xyz_batch_jax: floor(s / h) of s1 = x, s2 = x / 2 + y sqrt(3) / 2, s3 = z; biased, masked, packed
+    // tile_ids_from_xyz_batch_jax: floor(s / h) of s1 = x, s2 = x / 2 + y sqrt(3) / 2, s3 = z (pack_tile)
     const int64_t c1 = (int64_t)floor(mw[0] / h);
     const int64_t c2 = (int64_t)floor((mw[0] * 0.5 + mw[1] * s3h) / h);
     const int64_t cz = (int64_t)floor(mw[2] / h);
-    const int64_t bias = (int64_t)1 << 20, mask = ((int64_t)1 << 21) - 1;
-    const int64_t key = (((c1 + bias) & mask) << 42) | (((c2 + bias) & mask) << 21) | ((cz + bias) & mask);
-    const bool in = key == key_a;
+    const bool in = pack_tile(c1, c2, cz) == key_a;
     intile[i] = in ? 1 : 0;
     cnt += in ? 1 : 0;
   }
@@ -303,8 +267,11 @@ __global__ void __launch_bounds__(kMuWG) k_mu_plan(MuArgs A, PlanOut P) {
     P.indices[o] = (int32_t)i;
     P.valid[o] = vn ? 1 : 0;
     P.w[o] = wsel[q];
-    mu_to_world(Rt, A.pose, A.eps_lift, L, A.in.Lambdas + 9 * i, A.in.thetas + 3 * i,
-                A.in.etas + (int64_t)3 * L * i, P.Lam + 9 * o, P.th + 3 * o, P.et + (int64_t)3 * L * o);
+    double Lw[9], tw[3];
+    gaussian_to_world(Rt, A.pose, A.eps_lift, L, A.in.Lambdas + 9 * i, A.in.thetas + 3 * i,
+                      A.in.etas + (int64_t)3 * L * i, Lw, tw, P.et + (int64_t)3 * L * o);
+    for (int e = 0; e < 9; ++e) P.Lam[9 * o + e] = Lw[e];
+    for (int e = 0; e < 3; ++e) P.th[3 * o + e] = tw[e];
     for (int e = 0; e < 3; ++e) P.col[3 * o + e] = A.in.colors[3 * i + e];
     P.src[o] = A.in.sources[i];
     if (vn) atomicAdd(&misc[3], 1);
@@ -348,18 +315,8 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, map && in && h_pose6 && h_cfg && out, "NULL argument");
-  GC_CHECK_ARG(ctx, map->m_slots > 0 && map->m_slots < (int64_t)INT32_MAX, "m_slots out of range");
-  GC_CHECK_ARG(ctx, map->n_lobes >= 1 && map->n_lobes <= kMuMaxLobes, "n_lobes must be in [1, 8]");
-  {
-    const char* lay_ = gc::map_layout_error(*map);
-    GC_CHECK_ARG(ctx, lay_ == nullptr, lay_ ? lay_ : "");
-  }
-  GC_CHECK_ARG(ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
-                        map->last_supported_scan_seq && map->last_update_scan_seq && map->valid_mask,
-               "NULL map field");
-  const bool color = map->cam_mass != nullptr;
-  GC_CHECK_ARG(ctx, !color || (map->lidar_mass && map->rgb_cam_accum && map->rgb_cam_denom && map->rgb),
-               "colour fields must be all set or all NULL");
+  if (int rc = gc::check_map(ctx, map, (int64_t)INT32_MAX, false)) return rc;
+  GC_CHECK_ARG(ctx, map->valid_mask, "NULL map field");  // this entry's text for a missing valid_mask
   const int64_t N = in->N, K = in->K, m_tile = in->m_tile;
   const int na = in->n_active, k = in->k_insert;
   GC_CHECK_ARG(ctx, N >= 1 && N <= kMuMaxRows, "N must be in [1, GC_MAP_UPDATE_MAX_ROWS]");

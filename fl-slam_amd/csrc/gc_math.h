@@ -508,6 +508,34 @@ GC_DEV void solve3(const double* A, const double* b, double* x) {
   mat3_vec(Ai, b, x);
 }
 
+// Λ + ε I, the lifted precision of a primitive in information form
+GC_DEV void lifted3(const double* Lam, double eps_lift, double* Lr) {
+#pragma unroll
+  for (int q = 0; q < 9; ++q) Lr[q] = Lam[q] + ((q % 4 == 0) ? eps_lift : 0.0);
+}
+
+// mean of a primitive in information form: μ = (Λ + ε I)⁻¹ θ
+GC_DEV void prim_mean(const double* Lam, const double* theta, double eps_lift, double* mu) {
+  double Lr[9];
+  lifted3(Lam, eps_lift, Lr);
+  solve3(Lr, theta, mu);
+}
+
+// transform_gaussian_to_world (backend/pipeline.py:1248-1256) of one primitive with L lobes under the pose
+// (R, t): Λ_w = R Λ Rᵀ, μ_w = R μ + t, θ_w = Λ_w μ_w, η_w = R η (each lobe). Lw is read back for θ_w, so Lw
+// and tw are the caller's own arrays (registers); ew may be global memory. No output aliases an input.
+GC_DEV void gaussian_to_world(const double* R, const double* t, double eps_lift, int L, const double* Lb,
+                              const double* tb, const double* eb, double* Lw, double* tw, double* ew) {
+  double M3[9], mu[3], mw[3];
+  mat3_mul(R, Lb, M3);
+  mat3_mul_nt(M3, R, Lw);
+  prim_mean(Lb, tb, eps_lift, mu);
+  mat3_vec(R, mu, mw);
+  for (int q = 0; q < 3; ++q) mw[q] += t[q];
+  mat3_vec(Lw, mw, tw);
+  for (int l = 0; l < L; ++l) mat3_vec(R, eb + 3 * l, ew + 3 * l);
+}
+
 // p0 = Exp(α ξ)^{-1} p  (deskew_constant_twist.py:50-58: se3_exp then so3_exp of the rotvec)
 GC_DEV void deskew_point(const double* p, double alpha, const double* xi, double* out) {
   const double rho[3] = {alpha * xi[0], alpha * xi[1], alpha * xi[2]};

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 #include "gc_internal.h"
-#include "gc_mapslot.h"
+#include "gc_mapupdate.h"
 #include "gc_pipe.h"
 #include "gc_scanmap.h"
 
@@ -840,15 +840,7 @@ int32_t gc_pipeline_attach_primitive_map(gc_pipeline* p, const gc_primitive_map*
     p->smap_on = false;
     return GC_OK;
   }
-  GC_CHECK_ARG(p->ctx, map->m_slots > 0 && map->m_slots < (int64_t)0xFFFFFFFF, "m_slots out of range");
-  GC_CHECK_ARG(p->ctx, map->n_lobes >= 1 && map->n_lobes <= 8, "n_lobes must be in [1, 8]");
-  {
-    const char* lay_ = gc::map_layout_error(*map);
-    GC_CHECK_ARG(p->ctx, lay_ == nullptr, lay_ ? lay_ : "");
-  }
-  GC_CHECK_ARG(p->ctx, map->Lambdas && map->thetas && map->etas && map->weights && map->timestamps &&
-                           map->last_supported_scan_seq && map->last_update_scan_seq,
-               "NULL map field");
+  GC_TRY(gc::check_map_core(p->ctx, map, (int64_t)0xFFFFFFFF, false));  // lidar_mass is optional here (below)
   GC_CHECK_ARG(p->ctx, voxel_m > 0.0, "voxel_m must be positive");
   if (p->mstream) GC_TRY(gc::wait_stream(p->ctx, p->mstream, "the map-update stream before re-attaching"));
   GC_TRY(gc::scan_map_prepare(p->ctx, &p->smapW, p->P.n_cap, map->m_slots));

@@ -30,6 +30,7 @@
 
 #include "gc_internal.h"
 #include "gc_math.h"
+#include "gc_mapslot.h"
 #include "gc_sort.h"
 
 namespace gc {
@@ -40,7 +41,6 @@ constexpr int kRdMaxTile = 32;        // rendering.py:267, :320: tile_size is cl
 constexpr int kRdMaxCap = 256;        // splat records one raster step holds in LDS
 constexpr int kRdRec = 10;            // a record: mean 2, Sigma^-1 4, alpha 1, rgb 3
 constexpr int kRdMaxViews = 32;           // the views travel by value as a kernel argument (9 doubles each)
-constexpr int kRdMaxLobes = 8;
 
 // ------------------------------------------------------------------------------------------------
 // renderable batch
@@ -528,7 +528,7 @@ int32_t gc_renderable_batch_from_view(gc_ctx* ctx, const gc_map_view* view, doub
   if (int rc_j = join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, view && out && h_count, "NULL argument");
   GC_CHECK_ARG(ctx, view->n_tiles >= 0 && view->m_tile_view >= 0, "bad view shape");
-  GC_CHECK_ARG(ctx, view->n_lobes >= 1 && view->n_lobes <= kRdMaxLobes && out->n_lobes == view->n_lobes,
+  GC_CHECK_ARG(ctx, view->n_lobes >= 1 && view->n_lobes <= kMapMaxLobes && out->n_lobes == view->n_lobes,
                "n_lobes must be in [1, 8] and equal in the view and the batch");
   GC_CHECK_ARG(ctx, eps_lift == eps_lift, "NaN scalar argument");
   const int64_t V = (int64_t)view->n_tiles * view->m_tile_view;
@@ -602,7 +602,7 @@ int32_t gc_bev_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, 
   GC_CHECK_ARG(ctx, batch && h_P && h_view_dirs && h_cfg && out, "NULL argument");
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
-  GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kRdMaxLobes, "n_lobes must be in [1, 8]");
+  GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
   for (int q = 0; q < GC_BEV_CFG_LEN; ++q) GC_CHECK_ARG(ctx, fabs(h_cfg[q]) <= 1e300, "the configuration must be finite");
   for (int q = 0; q < 6 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_P[q]) <= 1e300, "P must be finite");
   for (int q = 0; q < 3 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_view_dirs[q]) <= 1e300, "view_dirs must be finite");

@@ -29,12 +29,12 @@
 #include "gc_blocksum.h"
 #include "gc_internal.h"
 #include "gc_math.h"
+#include "gc_mapslot.h"
 
 namespace gc {
 namespace {
 
 constexpr int kVpeMaxK = 16;
-constexpr int kVpeMaxLobes = 8;
 constexpr int kVpeT = 256;              // threads per workgroup, both passes
 constexpr int kVpeGroup = 8;            // lanes per measurement row
 constexpr int kVpeRows = kVpeT / kVpeGroup;  // rows per workgroup tile
@@ -84,8 +84,7 @@ __global__ void __launch_bounds__(kVpeT) k_vpe_collapse(
 #pragma unroll
     for (int q = 0; q < 9; ++q) Lr[q] = 0.0;
     if (vi) {
-#pragma unroll
-      for (int q = 0; q < 9; ++q) Lr[q] = Lam[9 * i + q] + ((q % 4 == 0) ? eps_lift : 0.0);
+      lifted3(Lam + 9 * i, eps_lift, Lr);
       for (int l = 0; l < L; ++l)
 #pragma unroll
         for (int q = 0; q < 3; ++q) es[q] += eta[(i * L + l) * 3 + q];
@@ -264,7 +263,7 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
   if (int rc_j = gc::join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, N >= 0 && H >= 0, "N and H must be >= 0");
   GC_CHECK_ARG(ctx, K >= 1 && K <= kVpeMaxK, "K must be in [1, 16]");
-  GC_CHECK_ARG(ctx, n_lobes >= 1 && n_lobes <= kVpeMaxLobes, "n_lobes must be in [1, 8]");
+  GC_CHECK_ARG(ctx, n_lobes >= 1 && n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
   GC_CHECK_ARG(ctx, view && h_cert, "NULL argument");
   GC_CHECK_ARG(ctx, N == 0 || (d_Lambdas && d_thetas && d_etas && d_valid && d_resp && d_pool_idx && d_row_masses),
                "NULL measurement / association buffer");

@@ -146,7 +146,10 @@ def _upload(dm, tile_id, tile):
 
 
 def _compare(dm, tile_id, ref, rtol=1e-12):
-    got = dm.download_tile(tile_id)
+    _compare_fields(dm.download_tile(tile_id), ref, rtol)
+
+
+def _compare_fields(got, ref, rtol=1e-12):
     for k, v in ref.items():
         g = got[k]
         if k in ("valid_mask", "primitive_ids", "last_supported_scan_seq", "last_update_scan_seq"):
@@ -259,3 +262,84 @@ def test_gpu_map_ops_edge_cases(ctx):
     _upload(big, 0, _random_tile(np.random.default_rng(1), 40, 1.0))
     res, cert, _ = PM.primitive_map_merge_reduce(big, 0, max_tile_size=20)  # budget cap
     assert res.n_merged == 0 and "merge_reduce_budget_cap" in cert.approximation_triggers
+
+
+def _slice_of(full, s0, n):
+    t = {k: v[s0:s0 + n] for k, v in full.items()}
+    t["valid_mask"] = t["valid_mask"].astype(bool)
+    return t
+
+
+@pytest.mark.gpu
+def test_gpu_per_tile_entries_on_an_unaligned_span(ctx):
+    """The C API takes any slot range, not only whole tiles: recency_inflate -> cull(max_primitives, the
+    sort runs) -> merge_reduce -> forget on the slots [5, 42) of a 2 x 64 packed map against the oracle's
+    per-tile operators on that slice (the bars of the sequence test above: 1e-12, 1e-10 from the merge's
+    3x3 inverses on), every other slot byte-identical to what was uploaded."""
+    import ctypes as C
+    from gcslam import _abi
+    from gcslam import primitive_map as PM
+    rng = np.random.default_rng(7)
+    S0, N, MAXP = 5, 37, 10
+    dm = PM.DevicePrimitiveMap(2, 64, ctx=ctx, packed=True)
+    for t_id in range(2):
+        _upload(dm, t_id, _random_tile(rng, 64))
+    before = dm.download()
+    ref = _slice_of(before, S0, N)
+
+    def check(rtol):
+        full = dm.download()
+        _compare_fields(_slice_of(full, S0, N), ref, rtol)
+        for k, v in full.items():
+            assert v[:S0].tobytes() == before[k][:S0].tobytes() and \
+                v[S0 + N:].tobytes() == before[k][S0 + N:].tobytes(), k
+
+    def call(name, *args):
+        _abi.call(name, ctx.handle, C.byref(dm.struct()), S0, N, *args, ctx=ctx)
+
+    st = np.zeros(3)
+    call("gc_primitive_map_recency_inflate", 37, 0.02, 0.05, st.ctypes.data)
+    ref, rst = O.primitive_map_recency_inflate(ref, 37, 0.02, 0.05)
+    assert st[0] == rst[0]
+    np.testing.assert_allclose(st[1:], rst[1:], rtol=1e-12)
+    check(1e-12)
+    n_valid = int(ref["valid_mask"].sum())
+    assert n_valid - int((ref["valid_mask"] & (ref["weights"] < 1e-3)).sum()) > MAXP  # the top-k branch sorts
+    out4 = np.zeros(4)
+    call("gc_primitive_map_cull", 1e-3, MAXP, out4.ctypes.data)
+    w_sum = float(ref["weights"].sum())
+    ref, n_c, mass = O.primitive_map_cull(ref, 1e-3, max_primitives=MAXP)
+    assert (out4[0], out4[3]) == (n_c, n_valid) and n_c > 0
+    np.testing.assert_allclose(out4[1:3], [mass, w_sum], rtol=1e-12)
+    check(1e-12)
+    out2 = np.zeros(2, np.int64)
+    call("gc_primitive_map_merge_reduce", 2.0, 16, O.EPS_PSD, O.EPS_LIFT, out2.ctypes.data)
+    ref, n_m = O.primitive_map_merge_reduce(ref, 2.0, 16)
+    assert (out2[0], out2[1]) == (n_m, int(ref["valid_mask"].sum())) and n_m > 0
+    check(1e-10)
+    call("gc_primitive_map_forget", 0.995)
+    ref = O.primitive_map_forget(ref, 0.995)
+    check(1e-10)
+
+
+@pytest.mark.gpu
+def test_gpu_recency_and_cull_on_a_grid_stride_tile(ctx):
+    """One tile of 240 x 256 + 1 slots: the first size at which the reduction grid is capped and a thread
+    visits two slots. Counts exact, sums at 1e-12 relative, the tile at the sequence test's bar."""
+    from gcslam import primitive_map as PM
+    M = 240 * 256 + 1
+    rng = np.random.default_rng(3)
+    dm = PM.DevicePrimitiveMap(1, M, ctx=ctx)
+    ref = _random_tile(rng, M)
+    _upload(dm, 0, ref)
+    _, _, eff, st = PM.primitive_map_recency_inflate(dm, [0], 37, 0.02, 0.05)
+    ref, rst = O.primitive_map_recency_inflate(ref, 37, 0.02, 0.05)
+    assert eff.realized == rst[0]
+    np.testing.assert_allclose(st.stale_precision_downscale_total, rst[1], rtol=1e-12)
+    np.testing.assert_allclose(st.staleness_cov_inflation_trace, rst[2], rtol=1e-12)
+    _compare(dm, 0, ref)
+    res, cert, _ = PM.primitive_map_cull(dm, 0, 1e-3, max_primitives=M // 2)
+    ref, n_c, mass = O.primitive_map_cull(ref, 1e-3, max_primitives=M // 2)
+    assert res.n_culled == n_c and n_c > 0 and not cert.exact
+    np.testing.assert_allclose(res.mass_dropped, mass, rtol=1e-12)
+    _compare(dm, 0, ref)
