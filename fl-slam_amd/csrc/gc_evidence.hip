@@ -46,8 +46,14 @@ GC_DEV double pose6_cond(double lmin, double lmax, double eps_psd, double* eigmi
   return mx / mn;
 }
 
-template <bool FOLD>
+// GIVEN (GC_LIDAR_GIVEN, gc_pipeline_scan_back): the LiDAR evidence is the map branch's full 22x22
+// L_lidar / h_lidar (P.lidar_L / P.lidar_h, pipeline.py:1010-1015, :1038-1039) and its aggregated
+// certificate row (P.lidar_cert, pipeline.py:1056-1067) instead of the bins' MF + planar blocks: a6's
+// certificate, a7, a8, the bin map's increment and every read of the bin statistics and the bin map are
+// compiled out; everything from the tempering on is the same code.
+template <bool FOLD, bool GIVEN = false>
 GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
+  static_assert(!(FOLD && GIVEN), "a given-evidence scan has no bins to finalize");
   extern __shared__ double sm[];
   double* Lpr = sm;          // L_pred
   double* Lev = Lpr + NN;    // L_raw -> L_ev
@@ -59,12 +65,12 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
   double* Sx = W3 + NN;      // 2NN + 4*22
   double* vec = Sx + 2 * NN + 4 * kDZ;  // 10 x 22
   double* red = vec + 10 * kDZ;         // 8
-  double* tab = red + 8;                // 64 x 16 per-bin table (kEvidenceTabDoubles)
-  double* acc = tab + kEvidenceTabDoubles;  // 32
+  [[maybe_unused]] double* tab = red + 8;                // 64 x 16 per-bin table (kEvidenceTabDoubles)
+  [[maybe_unused]] double* acc = tab + kEvidenceTabDoubles;  // 32
   double* sc = acc + 32;                // 128 scalars
   double* c6 = sc + 128;                // 6
-  double* mf = c6 + 6;                  // kMF  Matrix-Fisher record
-  double* pt = mf + kMF;                // kPT  planar record
+  [[maybe_unused]] double* mf = c6 + 6;                  // kMF  Matrix-Fisher record
+  [[maybe_unused]] double* pt = mf + kMF;                // kPT  planar record
   const int hl = blockIdx.x;
   const int t = threadIdx.x;
   const int n = kDZ, B = P.B;
@@ -82,12 +88,14 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
   for (int i = t; i < NN; i += kWG) {
     Lpr[i] = P.Lpred[(int64_t)hl * NN + i];
     Lev[i] = P.io_L[(int64_t)hl * NN + i];
+    if constexpr (GIVEN) Lev[i] += P.lidar_L[(int64_t)hl * NN + i];  // L_raw = L_io + L_lidar (:1038)
   }
   if (t < n) {
     hev[t] = P.io_h[(int64_t)hl * n + t];
+    if constexpr (GIVEN) hev[t] += P.lidar_h[(int64_t)hl * n + t];
     zl[t] = P.z[(int64_t)hl * n + t];
   }
-  const double* st = P.stats + (int64_t)hl * B * 38;
+  [[maybe_unused]] const double* st = P.stats + (int64_t)hl * B * 38;  // (GIVEN: no bin statistics)
   if constexpr (FOLD) {
     // the a6 finalize of this hypothesis folded in (scan_bins_pipeline, BinsFold): its chunk records
     // summed in chunk order (the split kernel's sums, bit for bit) into the per-bin table's space
@@ -119,94 +127,109 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
     }
     __syncthreads();  // the stats, aux and cert rows written above are read below (workgroup scope)
   }
-  // a6 certificate of the bins (binning.py:285-324): the cross-bin reductions of the split finalize's
-  // per-bin terms, on wave 0 in k_bins_finalize's wave_sum order (lane b = bin b, B <= 64); thread 0
-  // reads them back below (its own writes)
-  if (t < 64) {
-    double Nl = 0.0, N2l = 0.0, psdl = 0.0, epsl = 0.0, sfl = 0.0;
+  if constexpr (!GIVEN) {
+    // a6 certificate of the bins (binning.py:285-324): the cross-bin reductions of the split finalize's
+    // per-bin terms, on wave 0 in k_bins_finalize's wave_sum order (lane b = bin b, B <= 64); thread 0
+    // reads them back below (its own writes)
+    if (t < 64) {
+      double Nl = 0.0, N2l = 0.0, psdl = 0.0, epsl = 0.0, sfl = 0.0;
+      if (t < B) {
+        const double N = st[t * 38];
+        const double* ax = P.binaux + ((int64_t)hl * B + t) * 2;
+        Nl = N; N2l = N * N; psdl = ax[0]; epsl = ax[1]; sfl = N / (N + eps);
+      }
+      const double Nt = wave_sum(Nl), N2 = wave_sum(N2l), psd = wave_sum(psdl), mer = wave_max(epsl),
+                   sf = wave_sum(sfl);
+      if (t == 0) {
+        double* c = P.bincert + (int64_t)hl * 8;
+        c[0] = Nt * Nt / (N2 + eps);
+        c[1] = sf / (double)B;
+        c[2] = psd;
+        c[3] = mer;
+        c[7] = psd + mer;
+      }
+    }
+    GC_PHASE(P, 10);
+    // ---------------------------------------------- a7 MatrixFisher: per-bin cross-covariance
     if (t < B) {
-      const double N = st[t * 38];
-      const double* ax = P.binaux + ((int64_t)hl * B + t) * 2;
-      Nl = N; N2l = N * N; psdl = ax[0]; epsl = ax[1]; sfl = N / (N + eps);
+      const double* s = st + t * 38;
+      const double* m = P.map + t * kMapRec;
+      mf_bin_row(s[0], s + 1, m[12], m, eps, tab + t * 10);
+    } else if (t == 64) {  // R_pred on wave 1 beside the per-bin rows (B <= 64)
+      so3_exp(P.pose_pred + (int64_t)hl * 6 + 3, sc + 100);
     }
-    const double Nt = wave_sum(Nl), N2 = wave_sum(N2l), psd = wave_sum(psdl), mer = wave_max(epsl),
-                 sf = wave_sum(sfl);
-    if (t == 0) {
-      double* c = P.bincert + (int64_t)hl * 8;
-      c[0] = Nt * Nt / (N2 + eps);
-      c[1] = sf / (double)B;
-      c[2] = psd;
-      c[3] = mer;
-      c[7] = psd + mer;
+    __syncthreads();
+    GC_PHASE(P, 30);
+    sum_bins(tab, B, 10, acc);
+    GC_PHASE(P, 31);
+    // R_mf first; the rest of the MF record (information, δ, PSD, h) on wave 1 beside the planar rows,
+    // which need only R_mf (mf_rotation / mf_information: the same operations as mf_finalize; evidence
+    // 43.5 -> 39.4 us at H = 32, tools/r4_trace2.sh)
+    if (t == 0) mf_rotation(acc, mf, sc + 116);
+    __syncthreads();
+    GC_PHASE(P, 11);
+    // ---------------------------------------------- a8 planar translation WLS (R_hat = R_mf)
+    if (t < B) {
+      const double* s = st + t * 38;
+      const double* m = P.map + t * kMapRec;
+      const double* md = P.map_der + t * kMapDer;
+      planar_bin_row(mf, s[0], s + 13, s + 16, m[13], md + 4, md + 7, eps, tab + t * 13);
+    } else if (t == 64) {
+      mf_information(acc, sc + 100, sc + 116, eps, P.eps_psd, mf);
+    } else if (t == 128) {  // log R_mf for the tape on wave 2 beside the planar rows (B <= 64)
+      so3_log(mf, sc + 110);
     }
+    __syncthreads();
+    GC_PHASE(P, 32);
+    sum_bins(tab, B, 13, acc);
+    GC_PHASE(P, 33);
+    if (t == 0) planar_finalize(acc, P.map_misc[0], P.pose_pred + (int64_t)hl * 6, eps, P.eps_psd, pt);
+    __syncthreads();
+    GC_PHASE(P, 12);
+    // ---------------------------------------------- a9 evidence sum: L_raw = L_io + L_lidar
+    if (t < 9) {
+      const int i = t / 3, j = t % 3;
+      Lev[i * n + j] += pt[3 + t];                  // translation block [0:3, 0:3]
+      Lev[(3 + i) * n + (3 + j)] += mf[9 + t];      // rotation block [3:6, 3:6]
+      // the two 3x3 information matrices before their PSD projections, for the projection certificates
+      // (gc_certs.hip): L_rot = V diag(s1+s2, s0+s2, s0+s1) Vᵀ as mf_information forms it, L_trans =
+      // the summed WLS information masked by the z-scale as planar_finalize forms it
+      const double* V = sc + 116;
+      const double* s3 = mf + 24;
+      const double msk[3] = {1.0, 1.0, P.map_misc[0]};
+      double* raw = P.praw + (int64_t)hl * 18;
+      raw[t] = V[3 * i] * (s3[1] + s3[2]) * V[3 * j] + V[3 * i + 1] * (s3[0] + s3[2]) * V[3 * j + 1] +
+               V[3 * i + 2] * (s3[0] + s3[1]) * V[3 * j + 2];
+      raw[9 + t] = acc[t] * msk[i] * msk[j];
+    }
+    if (t < 3) { hev[t] += pt[12 + t]; hev[3 + t] += mf[18 + t]; }
+    __syncthreads();
+  } else {
+    __syncthreads();  // Lev / hev loaded
   }
-  GC_PHASE(P, 10);
-  // ---------------------------------------------- a7 MatrixFisher: per-bin cross-covariance
-  if (t < B) {
-    const double* s = st + t * 38;
-    const double* m = P.map + t * kMapRec;
-    mf_bin_row(s[0], s + 1, m[12], m, eps, tab + t * 10);
-  } else if (t == 64) {  // R_pred on wave 1 beside the per-bin rows (B <= 64)
-    so3_exp(P.pose_pred + (int64_t)hl * 6 + 3, sc + 100);
-  }
-  __syncthreads();
-  GC_PHASE(P, 30);
-  sum_bins(tab, B, 10, acc);
-  GC_PHASE(P, 31);
-  // R_mf first; the rest of the MF record (information, δ, PSD, h) on wave 1 beside the planar rows,
-  // which need only R_mf (mf_rotation / mf_information: the same operations as mf_finalize; evidence
-  // 43.5 -> 39.4 us at H = 32, tools/r4_trace2.sh)
-  if (t == 0) mf_rotation(acc, mf, sc + 116);
-  __syncthreads();
-  GC_PHASE(P, 11);
-  // ---------------------------------------------- a8 planar translation WLS (R_hat = R_mf)
-  if (t < B) {
-    const double* s = st + t * 38;
-    const double* m = P.map + t * kMapRec;
-    const double* md = P.map_der + t * kMapDer;
-    planar_bin_row(mf, s[0], s + 13, s + 16, m[13], md + 4, md + 7, eps, tab + t * 13);
-  } else if (t == 64) {
-    mf_information(acc, sc + 100, sc + 116, eps, P.eps_psd, mf);
-  } else if (t == 128) {  // log R_mf for the tape on wave 2 beside the planar rows (B <= 64)
-    so3_log(mf, sc + 110);
-  }
-  __syncthreads();
-  GC_PHASE(P, 32);
-  sum_bins(tab, B, 13, acc);
-  GC_PHASE(P, 33);
-  if (t == 0) planar_finalize(acc, P.map_misc[0], P.pose_pred + (int64_t)hl * 6, eps, P.eps_psd, pt);
-  __syncthreads();
-  GC_PHASE(P, 12);
-  // ---------------------------------------------- a9 evidence sum: L_raw = L_io + L_lidar
-  if (t < 9) {
-    const int i = t / 3, j = t % 3;
-    Lev[i * n + j] += pt[3 + t];                  // translation block [0:3, 0:3]
-    Lev[(3 + i) * n + (3 + j)] += mf[9 + t];      // rotation block [3:6, 3:6]
-    // the two 3x3 information matrices before their PSD projections, for the projection certificates
-    // (gc_certs.hip): L_rot = V diag(s1+s2, s0+s2, s0+s1) Vᵀ as mf_information forms it, L_trans =
-    // the summed WLS information masked by the z-scale as planar_finalize forms it
-    const double* V = sc + 116;
-    const double* s3 = mf + 24;
-    const double msk[3] = {1.0, 1.0, P.map_misc[0]};
-    double* raw = P.praw + (int64_t)hl * 18;
-    raw[t] = V[3 * i] * (s3[1] + s3[2]) * V[3 * j] + V[3 * i + 1] * (s3[0] + s3[2]) * V[3 * j + 1] +
-             V[3 * i + 2] * (s3[0] + s3[1]) * V[3 * j + 2];
-    raw[9 + t] = acc[t] * msk[i] * msk[j];
-  }
-  if (t < 3) { hev[t] += pt[12 + t]; hev[3 + t] += mf[18 + t]; }
-  __syncthreads();
   if (t == 0) {
     // aggregate_certificates([deskew, assign, moments, MF, planar]) then [ev, odom, imu, gyro]
-    const double* bc = P.bincert + (int64_t)hl * 8;
     const double* io = P.io_cert + (int64_t)hl * kIoCert;
-    const double* im = P.imu_out + (int64_t)hl * kImuOut;
-    const double retained = bc[6] / (P.budget[4] + eps);
-    const double ess_ev = (im[0] + exp(bc[4]) + bc[0] + 0.0 + 0.0) / 5.0;
-    const double sf_ev = (retained + bc[5] + bc[1] + 1.0 + 1.0) / 5.0;
-    const double ess_tot = (ess_ev + io[0] + io[1] + io[2]) / 4.0;
-    const double sf_tot = (sf_ev + io[3] + io[4] + io[5]) / 4.0;
-    const double exc = fmax(0.0, io[6]) + fmax(0.0, io[7]);
-    const double nll = mf[28] + pt[20] + io[8];
+    double ess_tot, sf_tot, exc, nll;
+    if constexpr (GIVEN) {
+      // aggregate_certificates([lidar, odom, imu, gyro]) with the LiDAR side already aggregated over
+      // [deskew, surfel, assoc, visual] (pipeline.py:1056-1067): mean support, max excitation, summed nll
+      const double* lc = P.lidar_cert + (int64_t)hl * kLidarCert;
+      ess_tot = (lc[0] + io[0] + io[1] + io[2]) / 4.0;
+      sf_tot = (lc[1] + io[3] + io[4] + io[5]) / 4.0;
+      exc = fmax(0.0, fmax(lc[3], io[6])) + fmax(0.0, fmax(lc[4], io[7]));
+      nll = lc[2] + io[8];
+    } else {
+      const double* bc = P.bincert + (int64_t)hl * 8;
+      const double* im = P.imu_out + (int64_t)hl * kImuOut;
+      const double retained = bc[6] / (P.budget[4] + eps);
+      const double ess_ev = (im[0] + exp(bc[4]) + bc[0] + 0.0 + 0.0) / 5.0;
+      const double sf_ev = (retained + bc[5] + bc[1] + 1.0 + 1.0) / 5.0;
+      ess_tot = (ess_ev + io[0] + io[1] + io[2]) / 4.0;
+      sf_tot = (sf_ev + io[3] + io[4] + io[5]) / 4.0;
+      exc = fmax(0.0, io[6]) + fmax(0.0, io[7]);
+      nll = mf[28] + pt[20] + io[8];
+    }
     // tempering β from raw-evidence sentinels (pipeline.py:1070-1111)
     double dp = 0.0, dp2 = 0.0, dv = 0.0, dv2 = 0.0;
     for (int k = 0; k < 6; ++k) { dp += Lev[15 * n + k] * Lev[15 * n + k]; dp2 += Lev[k * n + 15] * Lev[k * n + 15]; }
@@ -357,10 +380,14 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
   // a12 recompose: T from every operator's trigger magnitude (pipeline.py:1211), then δ' and X_new on
   // thread 0, beside the second phase of Σ_post -> W2 (also the next scan's predict Σ, P.Sig) on waves 1-3
   if (t == 0) {
-    const double* bc = P.bincert + (int64_t)hl * 8;
     const double trig_budget = 1e-12 / (P.budget[0] + 1e-12);
     double T = trig_budget + P.pred_cert[(int64_t)hl * kPredCert + 7] + P.io_cert[(int64_t)hl * kIoCert + 9];
-    T += 0.0 + bc[7] + mf[30] + pt[22];                // deskew, assign (exact), moments, MF, planar
+    if constexpr (GIVEN) {
+      T += P.lidar_cert[(int64_t)hl * kLidarCert + 5];  // deskew, surfel, recency-inflate, assoc, visual
+    } else {
+      const double* bc = P.bincert + (int64_t)hl * 8;
+      T += 0.0 + bc[7] + mf[30] + pt[22];                // deskew, assign (exact), moments, MF, planar
+    }
     T += fabs(1.0 - sc[50]);                           // PowerTempering
     T += fabs(1.0 - (1.0 - s_dt)) + fabs(1.0 - (1.0 - s_ex));  // ExcitationPriorScaling
     T += fabs(1.0 - alpha);                            // FusionScale
@@ -452,7 +479,11 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
       if (t - 64 < 36) P.h0rec[6 + (t - 64)] = W2[((t - 64) / 6) * n + (t - 64) % 6];
       else if (t - 64 < 42) P.h0rec[42 + (t - 100)] = P.xi[(int64_t)hl * 6 + (t - 100)];
       wave_lds_sync();
-      for (int b = t - 64; b < B; b += 64) pushforward_bin(st + b * 38, sc + 80, sc + 89, W2, n, P.map_inc + b * kMapRec);
+      if constexpr (GIVEN) {  // no bin-map increment: step 12b (the primitive map's update) replaces it
+        for (int e = t - 64; e < B * kMapRec; e += 64) P.map_inc[e] = 0.0;
+      } else {
+        for (int b = t - 64; b < B; b += 64) pushforward_bin(st + b * 38, sc + 80, sc + 89, W2, n, P.map_inc + b * kMapRec);
+      }
       if (t == 64) GC_STAMP(P.io_parts, 35);
     }
   } else {
@@ -485,10 +516,16 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
     double* dg = P.diag + (int64_t)hl * kHypDiag;  // [0, 6): the world pose, k_combine_local
     dg[6] = sc[61]; dg[7] = sc[50]; dg[8] = alpha; dg[9] = s_dt; dg[10] = s_ex; dg[11] = rho;
     dg[12] = sc[63]; dg[13] = sc[60]; dg[14] = sc[53]; dg[15] = sc[51]; dg[16] = sc[52]; dg[17] = sc[56];
-    dg[18] = mf[30]; dg[19] = pt[22]; dg[20] = sc[62];
-    for (int k = 0; k < 3; ++k) dg[21 + k] = pt[k];       // t_wls
-    for (int k = 0; k < 3; ++k) dg[24 + k] = sc[110 + k];  // log R_mf
-    for (int k = 0; k < 3; ++k) dg[27 + k] = mf[24 + k];  // MF singular values
+    dg[20] = sc[62];
+    if constexpr (GIVEN) {
+      dg[18] = 0.0; dg[19] = 0.0;
+      for (int k = 21; k < 30; ++k) dg[k] = 0.0;  // no MF / planar solve in this mode
+    } else {
+      dg[18] = mf[30]; dg[19] = pt[22];
+      for (int k = 0; k < 3; ++k) dg[21 + k] = pt[k];       // t_wls
+      for (int k = 0; k < 3; ++k) dg[24 + k] = sc[110 + k];  // log R_mf
+      for (int k = 0; k < 3; ++k) dg[27 + k] = mf[24 + k];  // MF singular values
+    }
     for (int k = 0; k < 6; ++k) dg[30 + k] = P.xi[(int64_t)hl * 6 + k];
     double mu2 = 0.0;
     for (int k = 0; k < n; ++k) mu2 += mufin[k] * mufin[k];
@@ -502,6 +539,11 @@ GC_DEV void evidence_body(const PipeDev& P, const ScanArgs& S) {
 template <int OCC, bool FOLD>
 __global__ void __launch_bounds__(256, OCC) k_evidence(PipeDev P, ScanArgs S) {
   evidence_body<FOLD>(P, S);
+}
+// the GC_LIDAR_GIVEN form, a kernel of its own so that the bin path's instantiations keep their names
+template <int OCC>
+__global__ void __launch_bounds__(256, OCC) k_evidence_given(PipeDev P, ScanArgs S) {
+  evidence_body<false, true>(P, S);
 }
 
 // ==================================================================== a16 partial sums (local)
@@ -662,6 +704,9 @@ __global__ void __launch_bounds__(256) k_combine_final(PipeDev P, ScanArgs S) {
     // reads the map): γ·map + increments of hypothesis 0 (bin_atlas.py:137-163, :232-257), the
     // increments reduced in the same rank order as workgroup 0's record (0.0 + Σ_g, so the value
     // is the same whether or not workgroup 0 has already rewritten an aliased single-rank record)
+    // GC_LIDAR_GIVEN: the bin map is not part of the scan (its evidence came from the primitive map):
+    // no forgetting step, the map stays bit for bit as it was
+    if (P.lidar_mode != 0) return;
     for (int e = t; e < P.B * kMapRec; e += kWG) {
       double s = 0.0;
       for (int g = 0; g < P.G; ++g) s += P.gather[(int64_t)g * PLn + kPMAP + e];
@@ -769,6 +814,18 @@ static hipError_t allow_big_lds(const void* fn, size_t bytes) {
 }
 hipError_t launch_evidence(const PipeDev& P, const ScanArgs& S, hipStream_t st) {
   const bool two = P.Hl > P.cus, fold = S.fin_part != nullptr;
+  if (P.lidar_mode != 0) {  // GC_LIDAR_GIVEN
+    if (fold) return hipErrorInvalidValue;
+#define GC_EVG(OCC)                                                                                      \
+  do {                                                                                                   \
+    if (hipError_t e = allow_big_lds((const void*)k_evidence_given<OCC>, lds_evidence())) return e; \
+    hipLaunchKernelGGL((k_evidence_given<OCC>), dim3(P.Hl), dim3(256), lds_evidence(), st, P, S);   \
+  } while (0)
+    if (two) GC_EVG(2);
+    else GC_EVG(1);
+#undef GC_EVG
+    return hipGetLastError();
+  }
 #define GC_EVL(OCC, FOLD)                                                                        \
   do {                                                                                           \
     if (hipError_t e = allow_big_lds((const void*)k_evidence<OCC, FOLD>, lds_evidence())) return e; \

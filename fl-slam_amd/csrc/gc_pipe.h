@@ -91,7 +91,14 @@ struct PipeDev {
   double *iw_cert;                         // [proc psd, proc nu, meas psd, meas nu]
   double *iwraw;                           // (kIwRawLen) the scan's unprojected IW blocks (k_combine_final):
                                            // process 7 x 6x6 masked, measurement 3 x 3x3 symmetrised
+  // GC_LIDAR_GIVEN (gc_pipeline_set_lidar_mode): the LiDAR evidence comes from the primitive-map branch
+  // (pipeline.py:778-1015) between the scan's two halves instead of the bins
+  int lidar_mode;                          // GC_LIDAR_BINS 0 / GC_LIDAR_GIVEN 1
+  double *lin_pose;                        // (Hl, 6) z_lin_pose (pipeline.py:751-755), k_pred_io
+  double *lidar_L, *lidar_h;               // (Hl, 22, 22), (Hl, 22) L_lidar / h_lidar (pipeline.py:1010-1015)
+  double *lidar_cert;                      // (Hl, kLidarCert) the aggregated LiDAR-side certificate row
 };
+constexpr int kLidarCert = 6;  // [ess_total, support_frac, nll_per_ess, exc_dt, exc_ex, trigger_sum]
 
 // Local hypothesis hl's bin tasks take the full feature set (its bin statistics carry the per-bin
 // direction scatter, columns 4:13): global hypothesis 0, whose scatter k_evidence pushes into the bin
@@ -155,6 +162,10 @@ bool predict_budget_inline(const PipeDev& P);
 hipError_t launch_budget_stats(const double* d_w, int64_t n_in, int64_t n_cap, double* part, double* out,
                                hipStream_t st);
 hipError_t launch_evidence(const PipeDev& P, const ScanArgs& S, hipStream_t st);
+// GC_LIDAR_GIVEN's front (gc_predio.hip): per local hypothesis the predict's L_pred half, the IMU/odom
+// branch when io, and the linearisation pose into P.lin_pose; the last workgroup to finish publishes
+// S.ticket into S.done_word (the launch is the slot's last reader)
+hipError_t launch_pred_io(const PipeDev& P, const ScanArgs& S, const double* d_odom, bool io, hipStream_t st);
 hipError_t launch_combine_local(const PipeDev& P, hipStream_t st);
 hipError_t launch_combine_final(const PipeDev& P, const ScanArgs& S, hipStream_t st,
                                 hipEvent_t done = nullptr);  // recorded at the launch's completion

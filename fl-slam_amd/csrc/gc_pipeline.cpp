@@ -125,6 +125,19 @@ struct gc_pipeline {
   // getter workspace (conditioning certificates), allocated with the pipeline: no hipMalloc / hipFree
   // (device-synchronising) on a getter a live node calls every scan
   double* ws = nullptr;
+  // GC_LIDAR_GIVEN (P.lidar_mode): the scan runs as scan_front -> set_lidar_evidence -> scan_back around
+  // the caller's map branch. front_state: 0 no front enqueued, 1 the front is enqueued, 2 its evidence
+  // is set too; front_S / front_slot / front_seq: the front's arguments, kept for the back
+  int front_state = 0;
+  gc::ScanArgs front_S{};
+  int front_slot = -1;
+  int64_t front_seq = 0;
+  double front_enq_ms = 0.0, front_wait_ms = 0.0;
+  // pinned staging of the LiDAR certificate rows (set_lidar_evidence enqueues their copy without a host
+  // wait; lc_done: the last copy out of it, waited for only before the buffer is rewritten, a scan later)
+  double* lc_host = nullptr;
+  hipEvent_t lc_done = nullptr;
+  bool lc_rec = false;
 };
 
 namespace {
@@ -230,6 +243,10 @@ int slot_alloc(gc_pipeline* p, gc_pipeline::Slot& s) {
   s.bpart = s.dev + Ly.bpart;
   return GC_OK;
 }
+
+// a scan is under way: its local half is enqueued and its finish is due, or (GC_LIDAR_GIVEN) its front is
+// enqueued and its back is due; the state the rest of the scan reads or writes is locked
+bool scan_open(const gc_pipeline* p) { return p->pending || p->front_state != 0; }
 
 #define GC_TRY(expr)             \
   do {                           \
@@ -344,7 +361,7 @@ int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const doub
   double** fields[] = {&P.X, &P.z, &P.L, &P.h, &P.stamp, &P.Lpred, &P.hpred, &P.pred_cert, &P.pose_pred, &P.xi,
                        &P.imu_out, &P.dPsiM, &P.stats, &P.bincert, &P.io_L, &P.io_h, &P.io_cert, &P.dPsiP,
                        &P.mu_fin, &P.diag, &P.mu_aux, &P.io_parts, &P.lpose, &P.Sig, &P.binaux, &P.hcond,
-                       &P.pred_mode, &P.praw, &P.pcert};
+                       &P.pred_mode, &P.praw, &P.pcert, &P.lin_pose, &P.lidar_L, &P.lidar_h, &P.lidar_cert};
   const size_t sizes[] = {(size_t)Hl * 6, (size_t)Hl * 22, (size_t)Hl * NN, (size_t)Hl * 22, (size_t)Hl,
                           (size_t)Hl * NN, (size_t)Hl * 22, (size_t)Hl * gc::kPredCert, (size_t)Hl * 6,
                           (size_t)Hl * 6, (size_t)Hl * gc::kImuOut, (size_t)Hl * 27, (size_t)Hl * B * 38,
@@ -352,7 +369,8 @@ int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const doub
                           (size_t)Hl * 252, (size_t)Hl * 22, (size_t)Hl * gc::kHypDiag, (size_t)Hl * gc::kMuAux,
                           (size_t)Hl * gc::kIoParts, (size_t)Hl * 36, (size_t)Hl * NN, (size_t)Hl * B * 2,
                           (size_t)Hl * 8, (size_t)Hl, (size_t)Hl * 18,
-                          ((size_t)Hl * (B + 2) + gc::kScanCerts) * 6};
+                          ((size_t)Hl * (B + 2) + gc::kScanCerts) * 6, (size_t)Hl * 6, (size_t)Hl * NN,
+                          (size_t)Hl * 22, (size_t)Hl * gc::kLidarCert};
   for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]) && rc == GC_OK; ++i) rc = dalloc(p, sizes[i], fields[i]);
   double** shared[] = {&P.weights, &P.Q, &P.bins, &P.map, &P.map_der, &P.map_misc, &P.map_inc, &P.nu_proc,
                        &P.Psi_proc, &P.nu_meas, &P.Psi_meas, &P.budget, &P.send, &P.gather, &P.comb, &P.iw_cert,
@@ -429,20 +447,22 @@ int32_t gc_pipeline_destroy(gc_pipeline* p) {
   if (p->cstream) (void)hipStreamDestroy(p->cstream);
   if (p->mstream) (void)hipStreamDestroy(p->mstream);
   if (p->done_word) (void)hipHostFree(p->done_word);
+  if (p->lc_host) (void)hipHostFree(p->lc_host);
+  if (p->lc_done) (void)hipEventDestroy(p->lc_done);
   delete p;
   return GC_OK;
 }
 
 int32_t gc_pipeline_set_bins(gc_pipeline* p, const double* h_bins) {
   GC_CHECK_ARG(nullptr, p && h_bins, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   return up(p, p->P.bins, h_bins, (size_t)p->P.B * 3);
 }
 
 int32_t gc_pipeline_set_beliefs(gc_pipeline* p, const double* h_X, const double* h_z, const double* h_L,
                                 const double* h_h, const double* h_stamp) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   const size_t Hl = p->P.Hl;
   p->sig_cached = false;
   p->hcond_scan = false;
@@ -466,13 +486,13 @@ int32_t gc_pipeline_get_beliefs(gc_pipeline* p, double* h_X, double* h_z, double
 
 int32_t gc_pipeline_set_weights(gc_pipeline* p, const double* h_w) {
   GC_CHECK_ARG(nullptr, p && h_w, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   return up(p, p->P.weights, h_w, p->P.H);
 }
 
 int32_t gc_pipeline_set_io_evidence(gc_pipeline* p, const double* h_L, const double* h_h, const double* h_cert) {
   GC_CHECK_ARG(nullptr, p && h_L && h_h && h_cert, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   const size_t Hl = p->P.Hl;
   GC_TRY(up(p, p->P.io_L, h_L, Hl * 484));
   GC_TRY(up(p, p->P.io_h, h_h, Hl * 22));
@@ -482,7 +502,7 @@ int32_t gc_pipeline_set_io_evidence(gc_pipeline* p, const double* h_L, const dou
 
 int32_t gc_pipeline_set_io_mode(gc_pipeline* p, int32_t mode) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_CHECK_ARG(p->ctx, mode == GC_IO_GIVEN || mode == GC_IO_COMPUTED, "io mode must be GC_IO_GIVEN or GC_IO_COMPUTED");
   p->io_mode = mode;
   return GC_OK;
@@ -537,7 +557,7 @@ int32_t gc_pipeline_get_io_evidence(gc_pipeline* p, double* h_L, double* h_h, do
 int32_t gc_pipeline_set_iw(gc_pipeline* p, const double* nu_proc, const double* Psi_proc, const double* nu_meas,
                            const double* Psi_meas) {
   GC_CHECK_ARG(nullptr, p && nu_proc && Psi_proc && nu_meas && Psi_meas, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_TRY(up(p, p->P.nu_proc, nu_proc, 7));
   GC_TRY(up(p, p->P.Psi_proc, Psi_proc, 252));
   GC_TRY(up(p, p->P.nu_meas, nu_meas, 3));
@@ -549,7 +569,7 @@ int32_t gc_pipeline_set_iw(gc_pipeline* p, const double* nu_proc, const double* 
 int32_t gc_pipeline_get_iw(gc_pipeline* p, double* nu_proc, double* Psi_proc, double* nu_meas, double* Psi_meas,
                            double* Q, double* cert4) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_TRY(down(p, nu_proc, p->P.nu_proc, 7));
   GC_TRY(down(p, Psi_proc, p->P.Psi_proc, 252));
   GC_TRY(down(p, nu_meas, p->P.nu_meas, 3));
@@ -560,7 +580,7 @@ int32_t gc_pipeline_get_iw(gc_pipeline* p, double* nu_proc, double* Psi_proc, do
 
 int32_t gc_pipeline_set_map(gc_pipeline* p, const double* h_map) {
   GC_CHECK_ARG(nullptr, p && h_map, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_TRY(up(p, p->P.map, h_map, (size_t)p->P.B * gc::kMapRec));
   GC_HIP(p->ctx, gc::launch_map_derive(p->P, p->ctx->stream));
   return GC_OK;
@@ -568,7 +588,7 @@ int32_t gc_pipeline_set_map(gc_pipeline* p, const double* h_map) {
 
 int32_t gc_pipeline_get_map(gc_pipeline* p, double* h_map, double* h_map_der, double* h_misc2) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_TRY(down(p, h_map, p->P.map, (size_t)p->P.B * gc::kMapRec));
   GC_TRY(down(p, h_map_der, p->P.map_der, (size_t)p->P.B * gc::kMapDer));
   return down(p, h_misc2, p->P.map_misc, 2);
@@ -681,7 +701,7 @@ int32_t gc_pipeline_stage_pointcloud2(gc_pipeline* p, int32_t slot, const uint8_
 int32_t gc_pipeline_attach_comm(gc_pipeline* p, gc_comm* comm) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
   GC_CHECK_ARG(p->ctx, comm == nullptr || gc::comm_size(comm) == p->P.G, "communicator size != world_size");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   p->comm = comm;
   if (p->P.G == 1) {
     // a single-rank pipeline with a communicator runs the real all-gather into a buffer of its own
@@ -759,8 +779,10 @@ static int32_t scan_finish_impl(gc_pipeline* p, const double* h_gather) {
   // cleared, so slot_wait_consumed falls back to an event recorded on the compute stream)
   if (fin_e >= 0) p->fin_ticket[fin_e] = p->pending_ticket;
   // the scan's remaining projection certificates (the record and IW blocks combine_final just used)
-  if (p->inscan_certs) GC_HIP(ctx, gc::launch_proj_certs(P, ctx->stream));
-  p->pcert_scan = p->inscan_certs;
+  // (a given-evidence scan has no bin or MF / planar projections: gc_pipeline_get_projection_certs is refused)
+  const bool pcerts = p->inscan_certs && P.lidar_mode == GC_LIDAR_BINS;
+  if (pcerts) GC_HIP(ctx, gc::launch_proj_certs(P, ctx->stream));
+  p->pcert_scan = pcerts;
   GC_TRY(stage_event(p, 6));
   if (smap) {
     auto& s = p->slots[p->pending_slot];
@@ -835,11 +857,14 @@ int32_t gc_pipeline_map_colors_stale(gc_pipeline* p) {
 
 int32_t gc_pipeline_attach_primitive_map(gc_pipeline* p, const gc_primitive_map* map, double voxel_m) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   if (!map) {
     p->smap_on = false;
     return GC_OK;
   }
+  GC_CHECK_ARG(p->ctx, p->P.lidar_mode == GC_LIDAR_BINS,
+               "GC_LIDAR_GIVEN takes no scan map (the in-scan voxel update belongs to the bin path; update the "
+               "primitive map after the scan, pipeline.py step 12b)");
   GC_TRY(gc::check_map_core(p->ctx, map, (int64_t)0xFFFFFFFF, false));  // lidar_mass is optional here (below)
   GC_CHECK_ARG(p->ctx, voxel_m > 0.0, "voxel_m must be positive");
   if (p->mstream) GC_TRY(gc::wait_stream(p->ctx, p->mstream, "the map-update stream before re-attaching"));
@@ -864,21 +889,21 @@ int32_t gc_pipeline_attach_primitive_map(gc_pipeline* p, const gc_primitive_map*
 int32_t gc_pipeline_set_scan_map_mode(gc_pipeline* p, int32_t mode) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
   GC_CHECK_ARG(p->ctx, mode == GC_SMAP_OWNER || mode == GC_SMAP_REPLICATED, "mode must be GC_SMAP_OWNER or GC_SMAP_REPLICATED");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   p->smap_mode = mode;
   return GC_OK;
 }
 
 int32_t gc_pipeline_get_scan_map_pose(gc_pipeline* p, double* h_out) {
   GC_CHECK_ARG(nullptr, p && h_out, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   return down(p, h_out, p->P.send + gc::rec_h0(p->P.B), gc::kH0Len);
 }
 
 int32_t gc_pipeline_get_scan_map_count(gc_pipeline* p, int64_t* n_slots) {
   GC_CHECK_ARG(nullptr, p && n_slots, "NULL argument");
   GC_CHECK_ARG(p->ctx, p->smap_on, "no PrimitiveMap attached");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   if (!smap_active(p)) {  // not this rank's map to update (GC_SMAP_OWNER on a rank without hypothesis 0)
     *n_slots = 0;
     return GC_OK;
@@ -893,6 +918,8 @@ int32_t gc_pipeline_get_scan_map_count(gc_pipeline* p, int64_t* n_slots) {
 
 static int32_t scan_local_impl(gc_pipeline* p, int32_t slot, double scan_start, double scan_end, double t_last,
                                double t_scan, double dt_sec, int64_t scan_count) {
+  GC_CHECK_ARG(p->ctx, p->P.lidar_mode == GC_LIDAR_BINS,
+               "GC_LIDAR_GIVEN runs a scan as gc_pipeline_scan_front / set_lidar_evidence / scan_back");
   GC_CHECK_ARG(p->ctx, !p->pending, "the previous scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_CHECK_ARG(p->ctx, slot >= 0 && slot < GC_PIPE_MAX_SLOTS && p->slots[slot].n_in > 0, "scan slot not staged");
   GC_CHECK_ARG(p->ctx, p->io_mode == GC_IO_GIVEN || p->slots[slot].has_odom,
@@ -958,9 +985,169 @@ int32_t gc_pipeline_scan_local(gc_pipeline* p, int32_t slot, double scan_start, 
   return rc;
 }
 
+// ------------------------------------------------------------------ GC_LIDAR_GIVEN: front / evidence / back
+int32_t gc_pipeline_set_lidar_mode(gc_pipeline* p, int32_t mode) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_CHECK_ARG(p->ctx, mode == GC_LIDAR_BINS || mode == GC_LIDAR_GIVEN, "lidar mode must be GC_LIDAR_BINS or GC_LIDAR_GIVEN");
+  GC_CHECK_ARG(p->ctx, !p->pending && p->front_state == 0, "a scan is pending (gc_pipeline_scan_back / gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !p->smap_on, "a scan map is attached (gc_pipeline_attach_primitive_map(p, NULL, 0) first)");
+  p->P.lidar_mode = mode;
+  return GC_OK;
+}
+
+static int32_t scan_front_impl(gc_pipeline* p, int32_t slot, double scan_start, double scan_end, double t_last,
+                               double t_scan, double dt_sec, int64_t scan_count) {
+  GC_CHECK_ARG(p->ctx, p->P.lidar_mode == GC_LIDAR_GIVEN, "gc_pipeline_scan_front needs GC_LIDAR_GIVEN (gc_pipeline_set_lidar_mode)");
+  GC_CHECK_ARG(p->ctx, p->front_state == 0, "a front is already enqueued (gc_pipeline_scan_back first)");
+  GC_CHECK_ARG(p->ctx, !p->pending, "the previous scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, slot >= 0 && slot < GC_PIPE_MAX_SLOTS && p->slots[slot].n_in > 0, "scan slot not staged");
+  GC_CHECK_ARG(p->ctx, p->io_mode == GC_IO_GIVEN || p->slots[slot].has_odom,
+               "GC_IO_COMPUTED needs the slot's odometry (gc_pipeline_stage_odom)");
+  gc_ctx* ctx = p->ctx;
+  auto& s = p->slots[slot];
+  if (s.ready_rec) GC_TRY(wait_event(p, s.ready));  // as scan_local: the host waits for the slot's copy
+  gc::ScanArgs S{s.imu_t, s.imu_g, s.imu_a, scan_start, scan_end, t_last, t_scan, dt_sec,
+                 scan_count >= 1 ? 1.0 : 0.0, s.w, s.n_in, p->stage_budget ? s.budget : nullptr, s.t, p->sig_cached ? 1 : 0};
+  gc::PipeDev& P = p->P;
+  GC_TRY(stage_event(p, 0));
+  GC_HIP(ctx, gc::launch_predict_imu(P, S, ctx->stream));
+  GC_TRY(stage_event(p, 1));
+  // the L_pred half, the IMU/odom branch and the linearisation pose; nothing after this launch reads
+  // the slot, so it publishes the scan's ticket itself (there is no bins launch to do it)
+  ++p->ticket;
+  gc::ScanArgs Sf = S;
+  Sf.done_word = p->done_word;
+  Sf.ticket = p->ticket;
+  GC_HIP(ctx, gc::launch_pred_io(P, Sf, s.odom, p->io_mode == GC_IO_COMPUTED, ctx->stream));
+  s.consumed_ticket = p->ticket;
+  p->pending_ticket = p->ticket;
+  GC_TRY(stage_event(p, 2));
+  p->front_S = S;
+  p->front_slot = slot;
+  p->front_seq = scan_count;
+  p->front_state = 1;
+  return GC_OK;
+}
+
+int32_t gc_pipeline_scan_front(gc_pipeline* p, int32_t slot, double scan_start, double scan_end, double t_last,
+                               double t_scan, double dt_sec, int64_t scan_count) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  const double t0 = now_ms();
+  p->wait_acc_ms = 0.0;
+  const int32_t rc = scan_front_impl(p, slot, scan_start, scan_end, t_last, t_scan, dt_sec, scan_count);
+  p->front_wait_ms = p->wait_acc_ms;
+  p->front_enq_ms = now_ms() - t0 - p->wait_acc_ms;
+  return rc;
+}
+
+int32_t gc_pipeline_front_poses(gc_pipeline* p, const double** d_lin_pose, const double** d_pose_pred) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_CHECK_ARG(p->ctx, p->front_state != 0, "no front is enqueued (gc_pipeline_scan_front)");
+  if (d_lin_pose) *d_lin_pose = p->P.lin_pose;
+  if (d_pose_pred) *d_pose_pred = p->P.pose_pred;
+  return GC_OK;
+}
+
+int32_t gc_pipeline_get_front_poses(gc_pipeline* p, double* h_lin_pose, double* h_pose_pred) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_TRY(down(p, h_lin_pose, p->P.lin_pose, (size_t)p->P.Hl * 6));
+  return down(p, h_pose_pred, p->P.pose_pred, (size_t)p->P.Hl * 6);
+}
+
+int32_t gc_pipeline_get_front_hyp0(gc_pipeline* p, double* h_out13) {
+  GC_CHECK_ARG(nullptr, p && h_out13, "NULL argument");
+  GC_CHECK_ARG(p->ctx, p->front_state != 0, "no front is enqueued (gc_pipeline_scan_front)");
+  // three small copies, one wait: local hypothesis 0's [xi_body 6 | ess_imu | pose_pred 6]
+  const hipMemcpyKind k = hipMemcpyDeviceToHost;
+  GC_HIP(p->ctx, hipMemcpyAsync(h_out13, p->P.xi, 6 * sizeof(double), k, p->ctx->stream));
+  GC_HIP(p->ctx, hipMemcpyAsync(h_out13 + 6, p->P.imu_out, sizeof(double), k, p->ctx->stream));
+  GC_HIP(p->ctx, hipMemcpyAsync(h_out13 + 7, p->P.pose_pred, 6 * sizeof(double), k, p->ctx->stream));
+  p->hs[GC_HS_D2H_BYTES] += 13.0 * sizeof(double);
+  return sync_counted(p);
+}
+
+int32_t gc_pipeline_get_front_twists(gc_pipeline* p, double* h_xi, double* h_ess_imu) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_TRY(down(p, h_xi, p->P.xi, (size_t)p->P.Hl * 6));
+  if (!h_ess_imu) return GC_OK;
+  std::vector<double> io((size_t)p->P.Hl * gc::kImuOut);
+  GC_TRY(down(p, io.data(), p->P.imu_out, io.size()));
+  for (int h = 0; h < p->P.Hl; ++h) h_ess_imu[h] = io[(size_t)h * gc::kImuOut];
+  return GC_OK;
+}
+
+int32_t gc_pipeline_set_lidar_evidence(gc_pipeline* p, const double* d_L, const double* d_h, const double* h_cert,
+                                       int32_t cert_rows) {
+  GC_CHECK_ARG(nullptr, p && d_L && d_h && h_cert, "NULL argument");
+  GC_CHECK_ARG(p->ctx, p->front_state != 0 && !p->pending,
+               "the LiDAR evidence is set between gc_pipeline_scan_front and gc_pipeline_scan_back");
+  const size_t Hl = (size_t)p->P.Hl;
+  GC_CHECK_ARG(p->ctx, cert_rows == 1 || (size_t)cert_rows == Hl, "cert_rows must be 1 (broadcast) or the local hypothesis count");
+  // device to device on the pipeline's stream: ordered after the launch that wrote them there
+  GC_HIP(p->ctx, hipMemcpyAsync(p->P.lidar_L, d_L, Hl * 484 * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
+  GC_HIP(p->ctx, hipMemcpyAsync(p->P.lidar_h, d_h, Hl * 22 * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
+  // the certificate rows through a pinned buffer, enqueued like the two copies above: no host wait here
+  // (the buffer's previous copy, a scan ago, has long completed)
+  const size_t nb = Hl * gc::kLidarCert * sizeof(double);
+  if (!p->lc_host) {
+    GC_HIP(p->ctx, hipHostMalloc((void**)&p->lc_host, nb, hipHostMallocDefault));
+    GC_HIP(p->ctx, hipEventCreateWithFlags(&p->lc_done, hipEventDisableTiming));
+  }
+  if (p->lc_rec) GC_TRY(wait_event(p, p->lc_done));
+  for (size_t h = 0; h < Hl; ++h)
+    std::memcpy(p->lc_host + h * gc::kLidarCert, h_cert + (cert_rows == 1 ? 0 : h * gc::kLidarCert),
+                gc::kLidarCert * sizeof(double));
+  GC_HIP(p->ctx, hipMemcpyAsync(p->P.lidar_cert, p->lc_host, nb, hipMemcpyHostToDevice, p->ctx->stream));
+  GC_HIP(p->ctx, hipEventRecord(p->lc_done, p->ctx->stream));
+  p->lc_rec = true;
+  p->hs[GC_HS_H2D_BYTES] += (double)nb;
+  p->front_state = 2;
+  return GC_OK;
+}
+
+int32_t gc_pipeline_get_lidar_evidence(gc_pipeline* p, double* h_L, double* h_h, double* h_cert) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  const size_t Hl = p->P.Hl;
+  GC_TRY(down(p, h_L, p->P.lidar_L, Hl * 484));
+  GC_TRY(down(p, h_h, p->P.lidar_h, Hl * 22));
+  return down(p, h_cert, p->P.lidar_cert, Hl * gc::kLidarCert);
+}
+
+static int32_t scan_back_impl(gc_pipeline* p) {
+  GC_CHECK_ARG(p->ctx, p->front_state != 0, "no front is enqueued (gc_pipeline_scan_front)");
+  GC_CHECK_ARG(p->ctx, p->front_state == 2, "the LiDAR evidence is not set (gc_pipeline_set_lidar_evidence)");
+  gc_ctx* ctx = p->ctx;
+  gc::PipeDev& P = p->P;
+  // a9 .. a15 on the given evidence (no a6 finalize, a7 or a8), then this rank's partial record
+  GC_HIP(ctx, gc::launch_evidence(P, p->front_S, ctx->stream));
+  p->sig_cached = true;
+  if (p->inscan_certs) GC_HIP(ctx, gc::launch_hyp_certs(P, ctx->stream));
+  p->hcond_scan = p->inscan_certs;
+  GC_TRY(stage_event(p, 3));
+  GC_HIP(ctx, gc::launch_combine_local(P, ctx->stream));
+  GC_TRY(stage_event(p, 4));
+  p->pending_S = p->front_S;
+  p->pending_slot = p->front_slot;
+  p->pending_seq = p->front_seq;
+  p->pending = true;
+  p->front_state = 0;
+  return GC_OK;
+}
+
+int32_t gc_pipeline_scan_back(gc_pipeline* p) {
+  GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  const double t0 = now_ms();
+  p->wait_acc_ms = 0.0;
+  const int32_t rc = scan_back_impl(p);
+  // the scan's local half for the host accounting: the front and this back
+  p->scan_wait_ms = p->front_wait_ms + p->wait_acc_ms;
+  p->scan_enq_ms = p->front_enq_ms + (now_ms() - t0 - p->wait_acc_ms);
+  return rc;
+}
+
 int32_t gc_pipeline_get_combined(gc_pipeline* p, double* h_out) {
   GC_CHECK_ARG(nullptr, p && h_out, "NULL argument");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_TRY(down(p, h_out, p->P.comb, GC_COMB_LEN));
   double* cc = h_out + 484 + 22 + 22 + 6;
   if (cc[2] != cc[2]) {
@@ -1021,8 +1208,9 @@ int32_t gc_pipeline_get_hyp_conditioning(gc_pipeline* p, double* h_out) {
 
 int32_t gc_pipeline_get_projection_certs(gc_pipeline* p, double* h_hyp, double* h_scan) {
   GC_CHECK_ARG(nullptr, p && h_hyp && h_scan, "NULL argument");
+  GC_CHECK_ARG(p->ctx, p->P.lidar_mode == GC_LIDAR_BINS, "GC_LIDAR_GIVEN has no bin, MF or planar projections");
   GC_CHECK_ARG(p->ctx, p->sig_cached, "no scan has run since the beliefs were set");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   const gc::PipeDev& P = p->P;
   // computed inside the scan (in-scan certificates), or now from the last scan's stored operands
   if (!p->pcert_scan) GC_HIP(p->ctx, gc::launch_proj_certs(P, p->ctx->stream));
@@ -1052,6 +1240,8 @@ int32_t gc_pipeline_get_hyp_stats(gc_pipeline* p, double* h_dPsi_proc, double* h
 
 int32_t gc_pipeline_get_bin_stats(gc_pipeline* p, double* h_stats, double* h_cert, double* h_xi) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
+  GC_CHECK_ARG(p->ctx, p->P.lidar_mode == GC_LIDAR_BINS,
+               "GC_LIDAR_GIVEN computes no bin statistics (the twists: gc_pipeline_get_front_twists)");
   GC_TRY(down(p, h_stats, p->P.stats, (size_t)p->P.Hl * p->P.B * 38));
   GC_TRY(down(p, h_cert, p->P.bincert, (size_t)p->P.Hl * 8));
   return down(p, h_xi, p->P.xi, (size_t)p->P.Hl * 6);
@@ -1059,7 +1249,7 @@ int32_t gc_pipeline_get_bin_stats(gc_pipeline* p, double* h_stats, double* h_cer
 
 int32_t gc_pipeline_set_stage_timing(gc_pipeline* p, int32_t on) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   if (on && !p->st_ev[0])
     for (hipEvent_t& e : p->st_ev) GC_HIP(p->ctx, hipEventCreate(&e));
   p->st_timing = on != 0;
@@ -1082,7 +1272,7 @@ int32_t gc_pipeline_stage_ms(gc_pipeline* p, float* h_ms) {
 
 int32_t gc_pipeline_set_predict_route(gc_pipeline* p, int32_t route) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   GC_CHECK_ARG(p->ctx, route == 0 || route == 1, "route must be 0 (split) or 1 (factorised)");
   p->P.predict_route = route;
   return GC_OK;
@@ -1090,14 +1280,14 @@ int32_t gc_pipeline_set_predict_route(gc_pipeline* p, int32_t route) {
 
 int32_t gc_pipeline_set_bin_scatter_all(gc_pipeline* p, int32_t on) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   p->P.bin_scatter_all = on != 0 ? 1 : 0;
   return GC_OK;
 }
 
 int32_t gc_pipeline_set_inscan_certs(gc_pipeline* p, int32_t on) {
   GC_CHECK_ARG(nullptr, p, "NULL pipeline");
-  GC_CHECK_ARG(p->ctx, !p->pending, "a scan's exchange is pending (gc_pipeline_scan_finish)");
+  GC_CHECK_ARG(p->ctx, !scan_open(p), "a scan's exchange is pending (gc_pipeline_scan_finish)");
   p->inscan_certs = on != 0;
   return GC_OK;
 }

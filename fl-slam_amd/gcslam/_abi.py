@@ -83,6 +83,15 @@ SIGNATURES = {
     "gc_pipeline_partial_len": [_vp],
     "gc_pipeline_get_partial": [_vp, _vp],
     "gc_pipeline_scan_finish": [_vp, _vp],
+    "gc_pipeline_set_lidar_mode": [_vp, _i32],
+    "gc_pipeline_scan_front": [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _i64],
+    "gc_pipeline_front_poses": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
+    "gc_pipeline_get_front_poses": [_vp, _vp, _vp],
+    "gc_pipeline_get_front_twists": [_vp, _vp, _vp],
+    "gc_pipeline_get_front_hyp0": [_vp, _vp],
+    "gc_pipeline_set_lidar_evidence": [_vp, _vp, _vp, _vp, _i32],
+    "gc_pipeline_get_lidar_evidence": [_vp, _vp, _vp, _vp],
+    "gc_pipeline_scan_back": [_vp],
     "gc_pipeline_get_combined": [_vp, _vp],
     "gc_pipeline_get_hyp_diag": [_vp, _vp],
     "gc_pipeline_get_hyp_conditioning": [_vp, _vp],
@@ -172,6 +181,8 @@ GC_MAP_DER = 17
 GC_IO_CERT = 10
 GC_IO_PARTS = 40
 GC_IO_GIVEN, GC_IO_COMPUTED = 0, 1
+GC_LIDAR_BINS, GC_LIDAR_GIVEN = 0, 1
+GC_LIDAR_CERT = 6
 GC_IOF_IN = 64
 GC_IOF_OUT = 484 + 22 + 16
 (GC_IOF_ODOM_QUADRATIC, GC_IOF_IMU_GYRO_ROTATION, GC_IOF_IMU_PREINT_FACTOR, GC_IOF_PLANAR_Z_PRIOR,

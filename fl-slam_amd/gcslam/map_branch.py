@@ -91,6 +91,7 @@ class MapBranchFront:
     residency: TileResidency
     map_branch_stats: Dict[str, float]  # the six floats of pipeline.py:920-925
     scan_seq: int
+    device: Optional[Dict[str, Any]] = None  # with device_out: L_lidar / h_lidar as DeviceArrays (no download)
 
 
 class MapBranch:
@@ -104,7 +105,11 @@ class MapBranch:
         self.config = config or MapBranchConfig()
         self.chart_id = chart_id
 
-    def front(self, measurement_batch, center_xyz, poses6, scan_seq: int) -> MapBranchFront:
+    def front(self, measurement_batch, center_xyz, poses6, scan_seq: int, device_out: bool = False
+              ) -> MapBranchFront:
+        """poses6 (H, 6): host array or DeviceArray. device_out=True keeps L_lidar / h_lidar on the device:
+        the front's L_lidar / h_lidar are then DeviceArrays (np.asarray downloads them), also under
+        `.device`."""
         cfg, dm = self.config, self.atlas_map
         ctx = dm.ctx
         center = np.asarray(center_xyz, np.float64).reshape(3)
@@ -138,7 +143,8 @@ class MapBranch:
                                                                   "primitive_map_recency_inflate")
 
         L_lidar, h_lidar, parts, vpe_cert = visual_pose_evidence_batched(assoc, measurement_batch, view, poses6,
-                                                                        cfg.eps_lift, cfg.eps_mass)
+                                                                        cfg.eps_lift, cfg.eps_mass,
+                                                                        device_out=device_out)
         stats = dict(zip(CANDIDATE_STATS, (float(v) for v in h_cand)))
         stats.update(staleness_inflation_strength=float(inflate_stats.staleness_inflation_strength),
                      staleness_cov_inflation_trace=float(inflate_stats.staleness_cov_inflation_trace),
@@ -147,7 +153,8 @@ class MapBranch:
                               map_view=view, measurement_batch=measurement_batch, active_tile_ids=active,
                               stencil_tile_ids=stencil, certs=[inflate_cert, assoc_cert],
                               inflate_stats=inflate_stats, residency=residency, map_branch_stats=stats,
-                              scan_seq=int(scan_seq))
+                              scan_seq=int(scan_seq),
+                              device=dict(L_lidar=L_lidar, h_lidar=h_lidar) if device_out else None)
 
     def update(self, front: MapBranchFront, pose_world, timestamp: float
                ) -> Tuple[PrimitiveMapUpdateResult, CertBundle, ExpectedEffect]:

@@ -62,17 +62,24 @@ def _association_arrays(ctx, association_result: PrimitiveAssociationResult, V: 
 
 def visual_pose_evidence_batched(association_result: PrimitiveAssociationResult, measurement_batch,
                                  map_view: DeviceMapView, poses6, eps_lift: float = GC_EPS_LIFT,
-                                 eps_mass: float = GC_EPS_MASS):
+                                 eps_mass: float = GC_EPS_MASS, device_out: bool = False):
     """The evidence of H linearisation poses poses6 (H, 6) = [t, rotvec] from one association, one
     call: (L_pose (H, 22, 22), h_pose (H, 22), parts (H, 26), cert_vec). parts rows are
     [L_trans (9) | h_trans (3) | L_rot (9) | h_rot (3) | cost_trans | cost_rot]; cert_vec =
     [n_valid_meas, n_valid_map, Σ row_masses, mean row mass] over the valid measurement rows. Row h is
     bitwise what the single-pose operator returns for pose h. measurement_batch is duck-typed as in
-    associate_primitives_ot: Lambdas (N,3,3), thetas (N,3), etas (N,L,3), valid_mask (N)."""
+    associate_primitives_ot: Lambdas (N,3,3), thetas (N,3), etas (N,L,3), valid_mask (N).
+    poses6 may be a DeviceArray (H, 6) on the view's context (used in place, no upload). With
+    device_out=True L_pose and h_pose come back as DeviceArrays with no download (the batched pipeline's
+    set_lidar_evidence takes them as they are); parts and cert_vec are host arrays either way."""
     ctx = map_view.ctx
     d_resp, d_idx, d_rowm, N, K = _association_arrays(ctx, association_result, map_view.count)
-    P = np.ascontiguousarray(poses6, np.float64).reshape(-1, 6)
-    H = P.shape[0]
+    if isinstance(poses6, _abi.DeviceArray):
+        H = int(np.prod(poses6.shape)) // 6
+        P = _abi.device_input(ctx, poses6, np.float64, (H, 6))
+    else:
+        P = np.ascontiguousarray(poses6, np.float64).reshape(-1, 6)
+        H = P.shape[0]
     etas = measurement_batch.etas
     L = int(np.shape(etas)[1])  # (N, L, 3)
     if int(np.prod(np.shape(measurement_batch.valid_mask))) != N:
@@ -90,6 +97,8 @@ def visual_pose_evidence_batched(association_result: PrimitiveAssociationResult,
               dh.ptr, dp.ptr, cert.ctypes.data, ctx=ctx)
     if H == 0:
         return np.zeros((0, D_Z, D_Z)), np.zeros((0, D_Z)), np.zeros((0, _abi.GC_VPE_PARTS)), cert
+    if device_out:
+        return dL, dh, dp.download(), cert
     Lp, hp, parts = _abi.download_many([dL, dh, dp])
     return Lp, hp, parts, cert
 

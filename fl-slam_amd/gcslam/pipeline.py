@@ -98,6 +98,7 @@ class BatchedScanPipeline:
         self.handle = h.value
         self._comm = None
         self._smap = None
+        self.lidar_given = False  # GC_LIDAR_BINS is the device default
         self.io_computed = True  # GC_IO_COMPUTED is the device default
         self.set_bins(create_fibonacci_atlas(self.B).dirs)
         self.set_weights(np.full(H_total, 1.0 / H_total))
@@ -203,6 +204,64 @@ class BatchedScanPipeline:
         """a1-a15 for this rank's hypotheses and its partial record; finish with finish_scan."""
         self._call("gc_pipeline_scan_local", int(slot), float(scan["scan_start"]), float(scan["scan_end"]),
                    float(scan["t_last"]), float(scan["t_scan"]), float(scan["dt_sec"]), int(scan_count))
+
+    # ---------------------------------------------------------------- GC_LIDAR_GIVEN: front / evidence / back
+    def set_lidar_mode(self, given: bool) -> None:
+        """LiDAR evidence source: False (default, GC_LIDAR_BINS) the bin path inside the scan; True
+        (GC_LIDAR_GIVEN) the primitive-map branch's L_lidar / h_lidar, set between scan_front and
+        scan_back (include/gcslam.h; gcslam.primitive_step shows the whole chain)."""
+        self._call("gc_pipeline_set_lidar_mode", _abi.GC_LIDAR_GIVEN if given else _abi.GC_LIDAR_BINS)
+        self.lidar_given = bool(given)
+
+    def scan_front(self, slot: int, scan: dict, scan_count: int) -> None:
+        """Predict, L_pred, the IMU/odom branch and the linearisation pose of a staged scan."""
+        self._call("gc_pipeline_scan_front", int(slot), float(scan["scan_start"]), float(scan["scan_end"]),
+                   float(scan["t_last"]), float(scan["t_scan"]), float(scan["dt_sec"]), int(scan_count))
+
+    def front_poses(self, device: bool = False):
+        """(z_lin_pose (Hl,6), pose_pred (Hl,6)) of the enqueued front (pipeline.py:751-755, :802):
+        host arrays, or with device=True non-owning DeviceArray views valid until the next front."""
+        if device:
+            a, b = C.c_void_p(), C.c_void_p()
+            self._call("gc_pipeline_front_poses", C.byref(a), C.byref(b))
+            return tuple(_abi.DeviceArray(self.ctx, (self.Hl, 6), np.float64, _base=self, _ptr=p.value) for p in (a, b))
+        lin, pp = np.empty((self.Hl, 6)), np.empty((self.Hl, 6))
+        self._call("gc_pipeline_get_front_poses", _p(lin), _p(pp))
+        return lin, pp
+
+    def front_twists(self):
+        """((Hl, 6) deskew twists xi_body, (Hl,) ESS of the scan-window IMU weights) of the last predict launch."""
+        o, e = np.empty((self.Hl, 6)), np.empty(self.Hl)
+        self._call("gc_pipeline_get_front_twists", _p(o), _p(e))
+        return o, e
+
+    def front_hyp0(self):
+        """(xi_body (6), ess_imu, pose_pred (6)) of local hypothesis 0 of the enqueued front: one wait."""
+        o = np.empty(13)
+        self._call("gc_pipeline_get_front_hyp0", _p(o))
+        return o[0:6], float(o[6]), o[7:13]
+
+    def set_lidar_evidence(self, L, h, cert) -> None:
+        """L_lidar (Hl,22,22) and h_lidar (Hl,22), DeviceArrays (used in place, copied on the stream) or
+        host arrays (uploaded first), and the LiDAR certificate rows (GC_LIDAR_CERT,) or (Hl, GC_LIDAR_CERT):
+        [ess_total, support_frac, nll_per_ess, exc_dt, exc_ex, trigger_sum]."""
+        dL = _abi.device_input(self.ctx, L, np.float64, (self.Hl, 22, 22))
+        dh = _abi.device_input(self.ctx, h, np.float64, (self.Hl, 22))
+        c = np.ascontiguousarray(cert, dtype=np.float64)
+        rows = 1 if c.ndim == 1 else c.shape[0]
+        c = c.reshape(rows, _abi.GC_LIDAR_CERT)
+        self._call("gc_pipeline_set_lidar_evidence", dL.ptr, dh.ptr, _p(c), rows)
+
+    def lidar_evidence(self):
+        """(L_lidar (Hl,22,22), h_lidar (Hl,22), cert (Hl, GC_LIDAR_CERT)) as last set."""
+        L, h, c = np.empty((self.Hl, 22, 22)), np.empty((self.Hl, 22)), np.empty((self.Hl, _abi.GC_LIDAR_CERT))
+        self._call("gc_pipeline_get_lidar_evidence", _p(L), _p(h), _p(c))
+        return L, h, c
+
+    def scan_back(self) -> None:
+        """Evidence sum, tempering, fusion, recompose, IW statistics and this rank's partial record on
+        the evidence of set_lidar_evidence; finish with finish_scan."""
+        self._call("gc_pipeline_scan_back")
 
     def partial(self) -> np.ndarray:
         """This rank's partial record of the pending scan (RECORD layout, partial_len(B) doubles)."""

@@ -333,6 +333,57 @@ int32_t gc_pipeline_scan_local(gc_pipeline* p, int32_t slot, double scan_start, 
 int32_t gc_pipeline_partial_len(const gc_pipeline* p);
 int32_t gc_pipeline_get_partial(gc_pipeline* p, double* h_record);
 int32_t gc_pipeline_scan_finish(gc_pipeline* p, const double* h_gather);
+/* LiDAR evidence source. GC_LIDAR_BINS (default): the legacy bin path, fused bins -> Matrix-Fisher ->
+ * planar WLS inside the scan. GC_LIDAR_GIVEN: the reference's current scan step (backend/pipeline.py:
+ * 778-1230), whose LiDAR evidence comes from the primitive map (surfels -> OT association ->
+ * visual_pose_evidence -> L_lidar, :998-1015). The scan is then split around the caller's map branch:
+ *  scan_front          predict and, per hypothesis, L_pred, the IMU/odom branch (:595-750) and the
+ *                      linearisation pose z_lin_pose (:751-755). No bins run; the launch is the slot's last
+ *                      reader and releases it for restaging.
+ *  front_poses         device pointers (Hl,6) to z_lin_pose and pose_pred, valid until the next front
+ *                      (get_front_poses downloads them, get_front_twists the deskew twists xi_body; in
+ *                      GC_LIDAR_BINS pose_pred is the last scan's and z_lin_pose is not computed).
+ *  set_lidar_evidence  L_lidar (Hl,22,22) and h_lidar (Hl,22) as DEVICE pointers on the pipeline's
+ *                      context, copied device to device on its stream (stream order is the only
+ *                      synchronisation with the launch that wrote them), and the LiDAR side's aggregated
+ *                      certificate rows (host; copied through a pinned buffer on the same stream, so the
+ *                      call does not wait for the device; cert_rows = 1 broadcasts one row, or Hl rows), GC_LIDAR_CERT
+ *                      doubles each: [ess_total, support_frac, nll_per_ess, exc_dt, exc_ex, trigger_sum]
+ *                      of aggregate_certificates([deskew, surfel, assoc, visual]) (:1056-1064); trigger_sum
+ *                      is the sum of those operators' (and the recency inflation's) trigger magnitudes
+ *                      (:1211). Without a map branch the evidence is eps_lift I, 0 (:1014-1015).
+ *  scan_back           L_raw = L_io + L_lidar (:1038-1039), the combined certificate (:1065-1067),
+ *                      tempering, excitation scaling, fusion, recompose, IW statistics, anchor drift
+ *                      (:1070-1230) and the partial record; then get_partial / scan_finish as after
+ *                      scan_local. The bin map is left bit for bit as it was (no forgetting step), the map
+ *                      increment in the record is zero, and diag entries 18, 19 and 21:30 are 0.
+ * GC_ERR_ARG: set_lidar_mode while a scan is under way or with a scan map attached (attaching one in
+ * GC_LIDAR_GIVEN is refused too: that update is the bin path's; step 12b, :1236-1327, is the caller's
+ * map update after the scan); scan_local / run_scan in GC_LIDAR_GIVEN; scan_front in GC_LIDAR_BINS or
+ * before the previous front's back; set_lidar_evidence outside front..back; scan_back without a front or
+ * without evidence; get_bin_stats / get_projection_certs in GC_LIDAR_GIVEN. Between front and back the
+ * state is locked as between scan_local and scan_finish. */
+#define GC_LIDAR_BINS 0
+#define GC_LIDAR_GIVEN 1
+#define GC_LIDAR_CERT 6
+int32_t gc_pipeline_set_lidar_mode(gc_pipeline* p, int32_t mode);
+int32_t gc_pipeline_scan_front(gc_pipeline* p, int32_t slot, double scan_start, double scan_end, double t_last,
+                               double t_scan, double dt_sec, int64_t scan_count);
+int32_t gc_pipeline_front_poses(gc_pipeline* p, const double** d_lin_pose, const double** d_pose_pred);
+int32_t gc_pipeline_get_front_poses(gc_pipeline* p, double* h_lin_pose, double* h_pose_pred);
+/* (Hl,6) deskew twists xi_body and (Hl) ESS of the scan-window IMU weights (DeskewConstantTwist's
+ * ess_imu, pipeline.py:530-560) of the last predict launch, in either mode; either pointer may be NULL.
+ * Like get_front_poses it is a plain read of the device buffers: before the first scan they hold zeros,
+ * and between scans the last scan's values. */
+int32_t gc_pipeline_get_front_twists(gc_pipeline* p, double* h_xi, double* h_ess_imu);
+/* The one small download a step needs between front and back (the reference's own sync, pipeline.py:811):
+ * local hypothesis 0's [xi_body 6 | ess_imu | pose_pred 6], three copies and one wait. GC_ERR_ARG without
+ * an enqueued front. */
+int32_t gc_pipeline_get_front_hyp0(gc_pipeline* p, double* h_out13);
+int32_t gc_pipeline_set_lidar_evidence(gc_pipeline* p, const double* d_L, const double* d_h, const double* h_cert,
+                                       int32_t cert_rows);
+int32_t gc_pipeline_get_lidar_evidence(gc_pipeline* p, double* h_L, double* h_h, double* h_cert);
+int32_t gc_pipeline_scan_back(gc_pipeline* p);
 int32_t gc_pipeline_get_combined(gc_pipeline* p, double* h_out);
 int32_t gc_pipeline_get_hyp_diag(gc_pipeline* p, double* h_diag);
 /* Per-hypothesis ConditioningCert (Hl, 2, 4) of the last scan's two 22x22 PSD projections,
@@ -416,7 +467,9 @@ int32_t gc_pipeline_exchange_ms(gc_pipeline* p, float* ms);
  * the IMU/odom branch, + finalize), evidence (a7-a15), combine_local, exchange, combine_final (a16, IW
  * apply, bin-map update), map_update (the attached PrimitiveMap's, 0 without one), total]. Each event
  * between kernels costs the stream ~1-5 us, so the timed product loop leaves it off. stage_ms
- * synchronises on the last event. */
+ * synchronises on the last event. In GC_LIDAR_GIVEN the stages keep their indices: "bins" is the front's
+ * second launch (L_pred, IMU/odom branch, z_lin_pose), and "evidence" runs from its end to the end of the
+ * evidence launch, so it includes whatever the caller enqueued on the stream between front and back. */
 #define GC_STAGE_N 8
 int32_t gc_pipeline_set_stage_timing(gc_pipeline* p, int32_t on);
 int32_t gc_pipeline_stage_ms(gc_pipeline* p, float* h_ms_out);
