@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(kSinkT) k_sinkhorn(int64_t N, const uint8_t* _
   for (int64_t i = threadIdx.x; i < N; i += kSinkT) {
     const bool vi = valid[i] != 0;
     const double a = vi ? (c.wprop ? wts[i] : 1.0) / sum_a : 0.0;
-    const double ui = u[i];
+    const double ui = c.iters > 0 ? u[i] : 1.0;  // no iteration: u = v = 1 (fori_loop(0, 0)), u never written
     double rm = 0.0, pc = 0.0;
     for (int q = 0; q < K; ++q) {
       const double pi = ui * kmat[i * K + q] * vv[q];

@@ -6,7 +6,12 @@ The reference's one test for this path is the budget-assertion test
 (test/test_budget_assertions.py:91-140), restated below for the device. Everything else is pinned
 by the oracle restatement ("parity unpinned" against reference outputs): candidate indices, tile
 ids and slots must match the oracle exactly; costs within 1e-10 relative; the Sinkhorn outputs
-(50 fixed iterations of powers 1/6) within 1e-8 relative."""
+(50 fixed iterations of powers 1/6) within 1e-8 relative.
+
+The shapes here are the default ones (r_xy = 1, r_z = 0, K = 1 or 8, L = 3, N <= 700, 50 iterations).
+The edges of both entries — N > 1024, zero iterations, the outer branches of A_vmf, larger stencils,
+K = 16, short rows, tied costs, other lobe counts and layouts — are in assoc_cases.py,
+test_association_edges.py (their conditions, no GPU) and test_gpu_association_edges.py."""
 
 import numpy as np
 import pytest
