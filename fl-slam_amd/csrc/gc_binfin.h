@@ -1,4 +1,4 @@
-// gc_binfin.h — the a6 bin finalize shared by the split finalize kernel (gc_points.hip) and the
+// gc_binfin.h — the a6 bin finalize shared by the split finalize kernel (gc_moments.hip) and the
 // evidence kernel's folded form (gc_evidence.hip): the chunk-record sums in chunk order and one bin's
 // moments -> p̄, Σ_p (PSD-projected), κ (binning.py:139-209).
 #pragma once
@@ -21,6 +21,11 @@ constexpr int NF_LEAN = 13;
 // keep the split finalize kernel (scan_bins_pipeline), so the sums never run into the table's neighbours
 constexpr int kEvidenceTabDoubles = 64 * 16;
 inline constexpr bool fold_record_fits(int B) { return B * NF_BASE + REC_EXTRA <= kEvidenceTabDoubles; }
+// (this kernel below: the split finalize, k_bins_finalize_split in gc_moments.hip)
+// up to this many chunk records per hypothesis (H = 256: 18, C5's 1024: 17) the evidence workgroup of
+// each hypothesis sums its own records (one more L2 round trip per 8 chunks at its start) in place of
+// this kernel's launch; more (H = 32: 80) keep the split kernel, which spreads them over 8 CUs
+constexpr int64_t kFoldChunks = 32;
 
 // Chunk records of one hypothesis summed entry-wise in chunk order (the max entry by fmax), KE
 // entries per thread and KU chunks per batch in flight; a ragged last batch loads zeros past the last

@@ -5,7 +5,7 @@
 //
 //  gc_wgla.h     wave_sum / wg_sum / wg_sum_n: DPP quad and mirror steps inside each 16-lane row, the
 //                four row totals by readlane as (r0 + r1) + (r2 + r3), the four waves as
-//                (w0 + w1) + (w2 + w3). Used by gc_points.hip, gc_evidence.hip, gc_ops.hip, gc_opsdev.h,
+//                (w0 + w1) + (w2 + w3). Used by gc_points.hip, gc_bins.hip, gc_binstask.h, gc_evidence.hip, gc_ops.hip, gc_opsdev.h,
 //                gc_belief.hip, gc_budget.h and gc_iofactors.h.
 //  this header   an xor butterfly inside the wave (__shfl_xor, off = 32..1: each step adds to a lane's
 //                partial the partial of lane ^ off, which covers a disjoint set of lanes; a + b = b + a,

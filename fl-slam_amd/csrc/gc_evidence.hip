@@ -816,30 +816,22 @@ hipError_t launch_evidence(const PipeDev& P, const ScanArgs& S, hipStream_t st) 
   const bool two = P.Hl > P.cus, fold = S.fin_part != nullptr;
   if (P.lidar_mode != 0) {  // GC_LIDAR_GIVEN
     if (fold) return hipErrorInvalidValue;
-#define GC_EVG(OCC)                                                                                      \
-  do {                                                                                                   \
-    if (hipError_t e = allow_big_lds((const void*)k_evidence_given<OCC>, lds_evidence())) return e; \
-    hipLaunchKernelGGL((k_evidence_given<OCC>), dim3(P.Hl), dim3(256), lds_evidence(), st, P, S);   \
-  } while (0)
-    if (two) GC_EVG(2);
-    else GC_EVG(1);
-#undef GC_EVG
-    return hipGetLastError();
+    return dispatch_bool(two, [&](auto two_tag) -> hipError_t {
+      constexpr int OCC = decltype(two_tag)::value ? 2 : 1;
+      if (hipError_t e = allow_big_lds((const void*)k_evidence_given<OCC>, lds_evidence())) return e;
+      hipLaunchKernelGGL((k_evidence_given<OCC>), dim3(P.Hl), dim3(256), lds_evidence(), st, P, S);
+      return hipGetLastError();
+    });
   }
-#define GC_EVL(OCC, FOLD)                                                                        \
-  do {                                                                                           \
-    if (hipError_t e = allow_big_lds((const void*)k_evidence<OCC, FOLD>, lds_evidence())) return e; \
-    hipLaunchKernelGGL((k_evidence<OCC, FOLD>), dim3(P.Hl), dim3(256), lds_evidence(), st, P, S);   \
-  } while (0)
-  if (two) {
-    if (fold) GC_EVL(2, true);
-    else GC_EVL(2, false);
-  } else {
-    if (fold) GC_EVL(1, true);
-    else GC_EVL(1, false);
-  }
-#undef GC_EVL
-  return hipGetLastError();
+  return dispatch_bool(two, [&](auto two_tag) -> hipError_t {
+    return dispatch_bool(fold, [&](auto fold_tag) -> hipError_t {
+      constexpr int OCC = decltype(two_tag)::value ? 2 : 1;
+      constexpr bool FOLD = decltype(fold_tag)::value;
+      if (hipError_t e = allow_big_lds((const void*)k_evidence<OCC, FOLD>, lds_evidence())) return e;
+      hipLaunchKernelGGL((k_evidence<OCC, FOLD>), dim3(P.Hl), dim3(256), lds_evidence(), st, P, S);
+      return hipGetLastError();
+    });
+  });
 }
 hipError_t launch_combine_local(const PipeDev& P, hipStream_t st) {
   const int nrec = (partial_len(P.B) + 15) / 16, npose = (P.Hl + kWG - 1) / kWG;

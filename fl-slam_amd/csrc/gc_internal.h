@@ -5,6 +5,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include "../../include/gcslam.h"
 
@@ -116,7 +117,7 @@ int carve_scratch(gc_ctx* ctx, Layout&& layout) {
 // (stream-ordered: a fill is enqueued on st when the table is new, grown or dirty)
 int run_table(gc_ctx* ctx, hipStream_t st, RunTableBuf* T, int64_t rows);
 
-// the table exp's 2048-entry table in device memory (gc_points.hip), enqueued once per context
+// the table exp's 2048-entry table in device memory (gc_bins.hip), enqueued once per context
 hipError_t init_exp_table(hipStream_t st);
 
 // Bounded host waits (fail fast). Poll the stream / event: ~spin_polls busy polls first (the wake-up
@@ -141,9 +142,42 @@ void comm_detach_ctx(gc_comm* c);
 hipError_t ensure_dyn_lds(const void* fn, size_t bytes);
 
 // GC_OK when kernel fn has no static LDS (its dynamic block starts at LDS address 0, which the fused
-// bins kernels' absolute table addressing relies on, gc_points.hip exp2s_shift8_n); checked once per
+// bins kernels' absolute table addressing relies on, gc_binsdev.h exp2s_shift_tab_n); checked once per
 // kernel and device
 int ensure_no_static_lds(gc_ctx* ctx, const void* fn);
+
+// Launch-site dispatch: a runtime value as a compile-time tag for a generic lambda, which reads it as
+// decltype(tag)::value and names its kernel instantiation with it (the idiom the kernels use on the device
+// side). Every launch site keeps its own predicates, LDS checks and error path inside its lambda; the
+// lambdas of one site return one type.
+template <typename F>
+auto dispatch_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+// bins per bin-lane of the bins kernels: B in [1, 64] -> 1..4
+inline int bpl_for(int B) { return (B + 15) / 16; }
+// f(std::integral_constant<int, BPL>{}, std::bool_constant<flag>{}) with BPL = bpl_for(B) (4 above 48) and
+// one flag of the site's own (FULL by the site's predicate at the bins sites, COV at the moment site)
+template <typename F>
+auto dispatch_bpl(int B, bool full, F&& f) {
+  return dispatch_bool(full, [&](auto full_tag) {
+    switch (bpl_for(B)) {
+      case 1: return f(std::integral_constant<int, 1>{}, full_tag);
+      case 2: return f(std::integral_constant<int, 2>{}, full_tag);
+      case 3: return f(std::integral_constant<int, 3>{}, full_tag);
+      default: return f(std::integral_constant<int, 4>{}, full_tag);
+    }
+  });
+}
+
+// the a6 finalize launches (gc_moments.hip), shared with the fused bins entries (gc_bins.hip): one
+// workgroup per hypothesis over its chunk records, and the batched pipeline's form split over bins
+// (grid (ceil(B / kFinBins), H); done_word: `ticket` stored once the launch runs)
+int32_t launch_bins_finalize(gc_ctx* ctx, int H, int B, int NF, int64_t chunks, const double* partials,
+                             double eps_psd, double eps_mass, double* stats, double* cert);
+int32_t launch_bins_finalize_split(gc_ctx* ctx, int H, int B, int NF, int64_t chunks, const double* partials,
+                                   double eps_psd, double eps_mass, double* stats, double* cert, double* aux,
+                                   int64_t* done_word, int64_t ticket, int n_full, int lean_records);
 
 }  // namespace gc
 

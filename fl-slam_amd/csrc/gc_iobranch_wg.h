@@ -1,6 +1,6 @@
 // gc_iobranch_wg.h — one hypothesis of the IMU/odom evidence branch (_compute_imu_odom_branch,
 // backend/pipeline.py:595-776) as a 256-thread workgroup body. The batched pipeline runs these
-// workgroups inside the fused bins launch (k_bins_io, gc_points.hip), beside the bin workgroups, so
+// workgroups inside the fused bins launch (k_bins_io, gc_bins.hip), beside the bin workgroups, so
 // the branch needs no stream fork / join of its own. Device code of the factors: gc_iofactors.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -16,6 +16,7 @@
 //  a15 process/measurement-noise IW       inverse_wishart_jax.py:35-185, measurement_noise_iw_jax.py:59-218
 //  a16 hypothesis_barycenter_projection   backend/operators/hypothesis.py:51-236
 //  a17 BeliefGaussianInfo.mean_increment / world pose   common/belief.py:373-425
+//  kappa_from_resultant_batch             kappa.py:130-169 (gc_domain_projection_psd_batch: gc_bins.hip)
 #include <hip/hip_runtime.h>
 #include "gc_internal.h"
 #include "gc_opsdev.h"
@@ -598,6 +599,12 @@ hipError_t allow_lds(const void* fn, size_t bytes) {
 }
 
 }  // namespace
+
+__global__ void k_kappa(int64_t n, const double* __restrict__ R, double eps_r, double d, double r0,
+                        double tau, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = kappa_blend(R[i], eps_r, d, r0, tau);
+}
 }  // namespace gc
 
 using namespace gc;
@@ -837,4 +844,14 @@ int32_t gc_hypothesis_barycenter(gc_ctx* ctx, int32_t H, const double* d_L, cons
   return GC_OK;
 }
 
+int32_t gc_kappa_from_resultant_batch(gc_ctx* ctx, int64_t n, const double* d_R, double eps_r, double d,
+                                      double r0, double tau, double* d_kappa_out) {
+  GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
+  GC_CHECK_ARG(ctx, n >= 0 && d_R && d_kappa_out, "bad arguments");
+  if (n == 0) return GC_OK;
+  hipLaunchKernelGGL(k_kappa, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, d_R, eps_r, d, r0,
+                     tau, d_kappa_out);
+  GC_LAUNCH_CHECK(ctx);
+  return GC_OK;
+}
 }  // extern "C"

@@ -180,7 +180,7 @@ hipError_t launch_proj_certs(const PipeDev& P, hipStream_t st);
 struct gc_ctx;
 namespace gc {
 // a1 -> a6 bins of the local hypotheses (+ the IMU/odom branch's workgroups in the same launch when
-// io) and their finalize into P.stats / P.bincert (gc_points.hip)
+// io) and their finalize into P.stats / P.bincert (gc_bins.hip)
 // (done_word: `ticket` stored once the bins have completed). With fold non-null and few chunk records
 // per hypothesis the finalize is left to k_evidence: fold receives the records, and the evidence
 // launch publishes the ticket

@@ -56,6 +56,7 @@ SIGNATURES = {
     "gc_scan_bin_moment_match": [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _dptr, _f64, _f64, _vp, _vp],
     "gc_scan_bins_fused": [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _f64, _dptr,
                            _f64, _f64, _vp, _vp, _i32],
+    "gc_bins_task_plan": [_i32, _i64, _i32, _vp],
     "gc_kappa_from_resultant_batch": [_vp, _i64, _vp, _f64, _f64, _f64, _f64, _vp],
     "gc_domain_projection_psd_batch": [_vp, _i32, _i32, _vp, _f64, _vp, _vp],
     "gc_pipeline_create": [_vp, _vp, _vp, C.POINTER(_vp)],

@@ -174,6 +174,18 @@ int32_t gc_scan_bins_fused(gc_ctx* ctx, int32_t H, int64_t n_in, int64_t n_cap, 
                            double eps_psd, double eps_mass, double* d_stats_out, double* d_cert_out,
                            int32_t iters);
 
+/* The task plan of the batched pipeline's bins launch (host-only: no context, no device): how the
+ * ceil(n_cap / 256) 256-point units of a budgeted scan are cut into chunks for a shard whose chunk
+ * geometry is sized for H_geom hypotheses (gc_pipeline geom_H, or the shard's own count) on a device
+ * of cu_count compute units. Chunks [0, k1) hold iters x 256 points, the next k2 iters_short x 256,
+ * the rest iters_tiny x 256; a hypothesis's records are summed in chunk order, so the plan fixes the
+ * order of summation.
+ * out8 = [iters, iters_short, iters_tiny, k1, k2, chunks, ahead (0/1), pullers]; ahead: the
+ * look-ahead form of the bins kernel runs (short tasks), otherwise the late-ticket form; pullers:
+ * the resident bin workgroups, 2 x cu_count.
+ * GC_ERR_ARG for H_geom < 1, n_cap < 1, cu_count < 1 or a NULL out8. */
+int32_t gc_bins_task_plan(int32_t H_geom, int64_t n_cap, int32_t cu_count, int64_t* out8);
+
 /* Budget reduction only (no gather): writes the 8 budget scalars. */
 int32_t gc_budget_stats(gc_ctx* ctx, const double* d_w, int64_t n_in, int64_t n_cap,
                         double* d_scalars_out);

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — records what the fused bins kernels computed before the softmax normaliser's
-batched 16-lane sum (gc_points.hip group16_sum2) went in, for the bit-identity checks of
+batched 16-lane sum (gc_binsdev.h group16_sum2) went in, for the bit-identity checks of
 tests/test_gpu_bins_zbatch.py. Run on an MI355X with the library built from the commit BEFORE that change:
 
     python tests/golden/make_bins_zbatch_parent.py

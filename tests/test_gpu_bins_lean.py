@@ -1,4 +1,4 @@
-"""The lean feature set of the persistent bins form (k_bins_io, gc_points.hip): the per-bin direction scatter
+"""The lean feature set of the persistent bins form (k_bins_io, gc_bins.hip): the per-bin direction scatter
 has one reader in a scan, the bin map's increment of global hypothesis 0, so every other hypothesis's bin
 statistics carry 0.0 in columns 4:13, and its long tasks accumulate 13 of the 19 per-bin moment features.
 

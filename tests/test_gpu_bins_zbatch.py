@@ -1,4 +1,4 @@
-"""The fused bins kernels with the softmax normaliser's batched 16-lane sum (gc_points.hip group16_sum2;
+"""The fused bins kernels with the softmax normaliser's batched 16-lane sum (gc_binsdev.h group16_sum2;
 B = 16 keeps the per-step butterfly, group16_sum): every instantiation of the grid form against the oracle
 chain, and bit identity with what the library computed before the batched form existed
 (tests/golden/bins_fused_parent.npz, pipeline_small_parent.npz; recorded by

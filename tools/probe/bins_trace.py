@@ -59,14 +59,16 @@ tk = tk[:nT]
 Hn = int(H)
 st, en = (tk[:, 0] - t0) / 100.0, (tk[:, 1] - t0) / 100.0
 du = en - st
-# Ticket order (TaskOrder, gc_points.hip). The late-ticket kernel runs when the tasks are 32 iterations long,
-# scan_bins_pipeline's rule: H x U >= 2 x pullers x 32 with U = 256 units of 256 points (the bench's 65,536-point
-# scans) and the pullers counted above (H >= 128 on 256 compute units). Its order: the chunks of the
+# Ticket order (TaskOrder, gc_binstask.h). The late-ticket kernel runs when the task plan says so
+# (gc_bins_task_plan's ahead flag off: 32-iteration tasks; asked for the bench's 65,536-point scans and the
+# pullers counted above, two per compute unit: H >= 128 on 256 compute units). Its order: the chunks of the
 # bin_scatter_full_count full-set hypotheses first (one, hypothesis 0: the bench is unsharded and leaves
 # set_bin_scatter_all off), then the lean-set hypotheses' tasks chunk-major. Otherwise (the look-ahead kernel),
 # or with "flat" as a third argument (a library from before the lean feature set): t = chunk * H + hypothesis.
 N_FULL = 1
-long_tasks = Hn * 256 >= 2 * int(pu.sum()) * 32
+plan = np.zeros(8, np.int64)
+_abi.call("gc_bins_task_plan", Hn, 65536, int(pu.sum()) // 2, plan.ctypes.data)
+long_tasks = plan[6] == 0
 if ORDER == "flat" or not long_tasks or Hn <= N_FULL:
     ch = np.arange(nT) // Hn
 else:

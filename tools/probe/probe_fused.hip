@@ -1,9 +1,9 @@
 // Dev probe (not product): the fused a1->a6 bins kernel at C3 size (64k points x 256 hypotheses),
-// times the shipped configuration (kFusedOcc / kFusedNacc are constants of gc_points.hip: a variant is
+// times the shipped configuration (kFusedOcc / kFusedNacc are constants of gc_binstask.h: a variant is
 // an edit of those constants, built here, never a knob of the product); times the
 // bin-distributed product kernel (k_bins_fused) and the lane-per-point experiment (k_bins_fused_lp,
 // kept here only).
-#include "../../fl-slam_amd/csrc/gc_points.hip"
+#include "../../fl-slam_amd/csrc/gc_bins.hip"
 #include <cstdio>
 #include <vector>
 

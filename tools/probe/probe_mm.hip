@@ -3,7 +3,8 @@
 #ifdef PROBE_NOMFMA
 #define __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, x, y, z) ((c) + (a) * (b))
 #endif
-#include "../../fl-slam_amd/csrc/gc_points.hip"
+#include "../../fl-slam_amd/csrc/gc_moments.hip"
+#include "../../fl-slam_amd/csrc/gc_bins.hip"  // k_soft_assign writes the responsibilities the pair leg reads
 #include <cstdio>
 #include <vector>
 
@@ -74,9 +75,13 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, 0, bins, (int64_t)3 * B, 8, -0.577, 0.577);
     hipEvent_t ev[3]; for (auto& e : ev) hipEventCreate(&e);
     const size_t sh = sizeof(double) * std::max<size_t>((size_t)4 * 32 * gc::kMomFS, (size_t)4 * B * 28);
+    // the kernel's dynamic LDS (exp table + wave slabs) and the table it copies
+    const size_t sa_sh = sizeof(double) * gc::sa_lds_doubles(3, true);
+    hipFuncSetAttribute((const void*)gc::k_soft_assign<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa_sh);
+    gc::init_exp_table(0);
     for (int r = 0; r < 4; ++r) {
       hipEventRecord(ev[0]);
-      hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), 0, 0, n, B, 4, dirs, bins, 10.0, resp, idx, sap);
+      hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), sa_sh, 0, n, B, 4, dirs, bins, 10.0, resp, idx, sap);
       hipEventRecord(ev[1]);
       hipLaunchKernelGGL((gc::k_moment_partials<3, true, true, 1>), dim3(32, H), dim3(256), sh, 0, n, B, 16, pts, covs, w, resp, lam, 0.1, 0.2, 0.3, part);
       hipEventRecord(ev[2]); hipEventSynchronize(ev[2]);

@@ -1,7 +1,7 @@
 // Dev probe (not product): write-bandwidth ceilings for the soft-assign output pattern vs the
 // product kernel. Build: hipcc -O3 --offload-arch=gfx950 -I include tools/probe/probe_sa.hip
 //   fl-slam_amd/gcslam/libgcslam.so -o tools/probe/probe_sa
-#include "../../fl-slam_amd/csrc/gc_points.hip"
+#include "../../fl-slam_amd/csrc/gc_bins.hip"
 #include <cstdio>
 #include <vector>
 
@@ -60,7 +60,11 @@ int main() {
   timeit("store_lin grid 4096", [&] { hipLaunchKernelGGL(k_store_lin, dim3(4096), dim3(256), 0, 0, resp, (int64_t)H * n * B / 2, 1.0); });
   timeit("store_lin grid 16384", [&] { hipLaunchKernelGGL(k_store_lin, dim3(16384), dim3(256), 0, 0, resp, (int64_t)H * n * B / 2, 1.0); });
   timeit("store_sa pattern", [&] { hipLaunchKernelGGL(k_store_sa, dim3(64, H), dim3(256), 0, 0, resp, n, 4, 1.0); });
-  timeit("k_soft_assign<3,true>", [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), 0, 0, n, B, 4, dirs, bins, 10.0, resp, idx, part); });
-  timeit("k_soft_assign<3,true> noidx", [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), 0, 0, n, B, 4, dirs, bins, 10.0, resp, (int32_t*)nullptr, part); });
+  // the kernel's dynamic LDS (exp table + wave slabs) and the table it copies
+  const size_t sa_sh = sizeof(double) * gc::sa_lds_doubles(3, true);
+  hipFuncSetAttribute((const void*)gc::k_soft_assign<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa_sh);
+  gc::init_exp_table(0);
+  timeit("k_soft_assign<3,true>", [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), sa_sh, 0, n, B, 4, dirs, bins, 10.0, resp, idx, part); });
+  timeit("k_soft_assign<3,true> noidx", [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(64, H), dim3(256), sa_sh, 0, n, B, 4, dirs, bins, 10.0, resp, (int32_t*)nullptr, part); });
   return 0;
 }

@@ -1,7 +1,7 @@
-// Dev probe (not product): the soft-assign contract kernel variants (ex[] in registers vs the
-// register-light recompute form) at C3 size, timed with events; FETCH/WRITE passes via rocprofv3.
+// Dev probe (not product): the soft-assign contract kernel (ex[] in registers; the register-light recompute
+// form it was measured against is retired) at C3 size, timed with events; FETCH/WRITE passes via rocprofv3.
 // Build: hipcc -O3 --offload-arch=gfx950 -I include tools/probe/probe_sa3.hip -o tools/probe/probe_sa3
-#include "../../fl-slam_amd/csrc/gc_points.hip"
+#include "../../fl-slam_amd/csrc/gc_bins.hip"
 #include <cstdio>
 #include <vector>
 
@@ -35,13 +35,15 @@ int main() {
     float ms; hipEventElapsedTime(&ms, e0, e1); ms /= 5;
     printf("%-34s %8.3f ms  %7.0f GB/s (algorithmic)\n", name, ms, bytes / (ms * 1e-3) / 1e9);
   };
+  // the kernel's dynamic LDS (exp table + wave slabs) and the table it copies
+  const size_t sa_sh = sizeof(double) * gc::sa_lds_doubles(3, true);
+  hipFuncSetAttribute((const void*)gc::k_soft_assign<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa_sh);
+  gc::init_exp_table(0);
   for (int iters : {4, 8}) {
     const int blocks = (int)((n + iters * 256 - 1) / (iters * 256));
     char nm[64];
     snprintf(nm, 64, "regs iters=%d", iters);
-    timeit(nm, [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true, false>), dim3(blocks, H), dim3(256), 0, 0, n, B, iters, dirs, bins, 10.0, resp, idx, part); });
-    snprintf(nm, 64, "recomp iters=%d", iters);
-    timeit(nm, [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true, true>), dim3(blocks, H), dim3(256), 0, 0, n, B, iters, dirs, bins, 10.0, resp, idx, part); });
+    timeit(nm, [&] { hipLaunchKernelGGL((gc::k_soft_assign<3, true>), dim3(blocks, H), dim3(256), sa_sh, 0, n, B, iters, dirs, bins, 10.0, resp, idx, part); });
   }
   printf("%s\n", hipGetErrorString(hipGetLastError()));
   return 0;
