@@ -167,6 +167,7 @@ SIGNATURES = {
     "gc_camera_measurement_batch": [_vp, _i64, _vp, _vp, _vp, _i64] + [_vp] * 11 + [_vp, _vp, _f64, _f64, _i32, _i32,
                                                                                     _i32, _f64] + [_vp] * 14,
     "gc_measurement_batch_from_camera_splats": [_vp, _i64] + [_vp] * 7 + [_i32, _i32, _i32, _f64] + [_vp] * 9,
+    "gc_camera_features_lift": [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp] + [_vp] * 12,
     "gc_renderable_batch_from_view": [_vp, _vp, _f64, _vp, C.POINTER(C.c_int64)],
     "gc_bev_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gc_render_ewa_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp],
@@ -221,6 +222,8 @@ GC_CAM_MAX_NEAR = 1024          # gc_camsplat.hip: in-radius LiDAR points one qu
 GC_CAM_MAX_POINTS = 1 << 22
 GC_CAM_MAX_QUERIES = 4096
 GC_CAM_MAX_FIT_POINTS = 256     # gc_camsplat.hip: one fitted point per thread
+GC_CAMFEAT_CFG_LEN = 24
+GC_CAMFEAT_AUX = 6
 
 
 class PipelineDims(C.Structure):

@@ -35,12 +35,14 @@ from .imu_odom_evidence import (ImuDependenceInflationResult, ImuGyroEvidenceRes
 from .visual_pose_evidence import (VisualPoseEvidenceResult, build_visual_pose_evidence_22d, visual_pose_evidence,
                                    visual_pose_evidence_batched)
 from .lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
-from .camera_splats import (CameraFeatures, CameraSplatDiagnostics, LidarCameraDepthFusionConfig, PinholeIntrinsics,
-                            camera_measurement_batch, feature_list_to_camera_batch, lidar_depth_evidence,
-                            measurement_batch_from_camera_splats)
+from .camera_splats import (CameraFeatures, CameraSplatDiagnostics, DeviceCameraFeatures,
+                            LidarCameraDepthFusionConfig, PinholeIntrinsics, camera_measurement_batch,
+                            feature_list_to_camera_batch, lidar_depth_evidence, measurement_batch_from_camera_splats)
+from .camera_features import VisualFeatureConfig, lift_camera_features, select_keypoints
 from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "VisualFeatureConfig", "lift_camera_features", "select_keypoints", "DeviceCameraFeatures",
     "CameraFeatures", "CameraSplatDiagnostics", "LidarCameraDepthFusionConfig", "PinholeIntrinsics",
     "camera_measurement_batch", "feature_list_to_camera_batch", "lidar_depth_evidence",
     "measurement_batch_from_camera_splats",

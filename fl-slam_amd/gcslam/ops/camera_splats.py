@@ -77,9 +77,52 @@ class CameraFeatures:
     has_color: np.ndarray      # (M,) bool
     xyz: np.ndarray            # (M, 3)
     cov_xyz: np.ndarray        # (M, 3, 3)
+    aux: Optional[np.ndarray] = None  # (M, GC_CAMFEAT_AUX) from lift_camera_features; nothing here reads it
 
     def __len__(self) -> int:
         return int(np.shape(self.u)[0])
+
+
+@dataclass
+class DeviceCameraFeatures:
+    """CameraFeatures in HBM, as lift_camera_features(..., device_out=True) leaves them: the same
+    names holding DeviceArrays laid out as gc_camera_measurement_batch reads them (uv one (M, 2) array,
+    the two flags uint8), plus aux (M, GC_CAMFEAT_AUX; camera_features.AUX_NAMES).
+    camera_measurement_batch passes the pointers on as they are."""
+    uv: "_abi.DeviceArray"
+    depth_Lambda_c: "_abi.DeviceArray"
+    depth_theta_c: "_abi.DeviceArray"
+    weight: "_abi.DeviceArray"
+    kappa_app: "_abi.DeviceArray"
+    mu_app: "_abi.DeviceArray"
+    has_mu_app: "_abi.DeviceArray"
+    color: "_abi.DeviceArray"
+    has_color: "_abi.DeviceArray"
+    xyz: "_abi.DeviceArray"
+    cov_xyz: "_abi.DeviceArray"
+    aux: "_abi.DeviceArray"
+
+    def __len__(self) -> int:
+        return int(self.uv.shape[0])
+
+    @property
+    def u(self) -> np.ndarray:
+        """Column 0 of uv on the host (a download: the columns are strided in HBM)."""
+        return np.ascontiguousarray(self.uv.download()[:, 0])
+
+    @property
+    def v(self) -> np.ndarray:
+        return np.ascontiguousarray(self.uv.download()[:, 1])
+
+    def to_host(self) -> CameraFeatures:
+        """The host CameraFeatures with the same values (one download when the arrays share a block)."""
+        names = [f.name for f in fields(self)]
+        h = dict(zip(names, _abi.download_many([getattr(self, k) for k in names])))
+        uv = h.pop("uv")
+        for k in ("has_mu_app", "has_color"):
+            h[k] = h[k].astype(bool)
+        return CameraFeatures(u=np.ascontiguousarray(uv[:, 0]), v=np.ascontiguousarray(uv[:, 1]),
+                              **{k: np.array(a) for k, a in h.items()})
 
 
 @dataclass
@@ -308,15 +351,16 @@ def _pack_features(features: CameraFeatures):
     return out
 
 
-def camera_measurement_batch(points_base, features: CameraFeatures, intrinsics: PinholeIntrinsics, R_base_camera,
+def camera_measurement_batch(points_base, features, intrinsics: PinholeIntrinsics, R_base_camera,
                              t_base_camera, timestamp_sec: float,
                              config: Optional[LidarCameraDepthFusionConfig] = None, *, pixel_sigma: float = 1.0,
                              n_feat: int = GC_N_FEAT, n_surfel: int = GC_N_SURFEL, eps_lift: float = GC_EPS_LIFT,
                              ctx=None, device_out: bool = False, return_diag: bool = False):
     """backend_node.py:1872-1925 in one device call: base-frame LiDAR points (N, 3; host array or the
-    DeviceArray deskew_constant_twist(..., device_out=True) returns) and the image's features -> the
-    camera slice of a fresh MeasurementBatch in the base frame (rows past min(M, n_feat) zero), which
-    extract_lidar_surfels takes as base_batch. With device_out the nine arrays stay in HBM as the
+    DeviceArray deskew_constant_twist(..., device_out=True) returns) and the image's features (a host
+    CameraFeatures, or the DeviceCameraFeatures lift_camera_features(..., device_out=True) returns,
+    whose arrays are read where they lie) -> the camera slice of a fresh MeasurementBatch in the base
+    frame (rows past min(M, n_feat) zero), which extract_lidar_surfels takes as base_batch. With device_out the nine arrays stay in HBM as the
     batch's fields and batch.device. With return_diag the result is (batch, CameraSplatDiagnostics).
     No features gives create_empty_measurement_batch, as feature_list_to_camera_batch does."""
     cfg = config or LidarCameraDepthFusionConfig()
@@ -335,17 +379,22 @@ def camera_measurement_batch(points_base, features: CameraFeatures, intrinsics: 
     n = _n_rows(points_base, 3, "points_base")
     m = len(features)
     _check_counts(n, m)
-    f = _pack_features(features)
+    on_device = isinstance(features, DeviceCameraFeatures)
+    f = None if on_device else _pack_features(features)
     if m == 0:
         empty = create_empty_measurement_batch(n_feat=n_feat, n_surfel=n_surfel)
         return (empty, None) if return_diag else empty
-    ctx = ctx or _abi.default_context()
+    ctx = ctx or (features.uv.ctx if on_device else _abi.default_context())
     dp = _abi.device_input(ctx, points_base, np.float64, (n, 3)) if n else None
-    uv = np.stack([f["u"], f["v"]], axis=1)
-    order = [uv, f["depth_Lambda_c"], f["depth_theta_c"], f["weight"], f["kappa_app"], f["mu_app"], f["has_mu_app"],
-             f["color"], f["has_color"], f["xyz"], f["cov_xyz"]]
-    dts = [np.uint8 if a.dtype == np.uint8 else np.float64 for a in order]
-    dev = _abi.upload_many(ctx, order, dts)
+    if on_device:  # the lift's arrays where they lie in HBM: no download, no upload
+        dev = [_abi.device_input(ctx, getattr(features, k), np.uint8 if k.startswith("has_") else np.float64,
+                                 (m,) + shp) for k, shp in (("uv", (2,)),) + _FEATURE_SHAPES[2:]]
+    else:
+        uv = np.stack([f["u"], f["v"]], axis=1)
+        order = [uv, f["depth_Lambda_c"], f["depth_theta_c"], f["weight"], f["kappa_app"], f["mu_app"],
+                 f["has_mu_app"], f["color"], f["has_color"], f["xyz"], f["cov_xyz"]]
+        dts = [np.uint8 if a.dtype == np.uint8 else np.float64 for a in order]
+        dev = _abi.upload_many(ctx, order, dts)
     extra = [((m, 3), np.float64), ((m, 3, 3), np.float64), ((m,), np.uint8), ((m, _abi.GC_CAM_EV), np.float64),
              ((m,), np.int32)]
     names, blk = _batch_block(ctx, n_feat + n_surfel, GC_VMF_N_LOBES, extra)

@@ -1179,6 +1179,44 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                                     double* d_fused_xyz, double* d_fused_cov, uint8_t* d_fused_flag,
                                     double* d_evidence, int32_t* d_counts);
 
+#define GC_CAMFEAT_CFG_LEN 24 /* the visual feature node's parameters in the order it declares them
+                                 (src/visual_feature_node.cpp:74-101): [depth_sample_mode (0 nearest,
+                                 1 median3, 2 median5, 3 hex), pixel_sigma, depth_model (0 linear,
+                                 1 quadratic), depth_sigma0, depth_sigma_slope, min_depth_m, max_depth_m,
+                                 depth_validity_slope, response_soft_scale, depth_scale, cov_reg_eps,
+                                 invalid_cov_inflate, hex_radius, quad_fit_radius, quad_fit_min_points,
+                                 quad_fit_lstsq_eps, student_t_nu, student_t_w_min, ma_tau,
+                                 ma_delta_inflate, kappa0, kappa_alpha, kappa_max, kappa_min] */
+#define GC_CAMFEAT_AUX 6      /* per keypoint: depth_sigma_c_sq (NaN without a valid depth), z_m (NaN
+                                 without), the depth window's valid count, the quadratic fit's point
+                                 count (0 without a valid depth), lam_min and K (0 without a fit) */
+/* The image side of the camera features (src/visual_feature_node.cpp:493-652 without ORB, and what
+   _feature_batch_to_list makes of the message, backend/backend_node.py:1589-1645): M keypoints d_kp
+   (M, 3) = (u, v, response) in f64, the depth image d_depth (float32, H x W, row-major, metres before
+   depth_scale) and the colour image d_rgb (uint8, H x W x 3; NULL: no colours, d_color 0 and
+   d_has_color 0) -> per keypoint depth_sample (:228-297; std::round, the window clipped to the image,
+   the element of rank size/2, the variance from 4 values up) or depth_sample_hex (:299-348),
+   student_t_effective_var (:350-369), depth_weight, response_weight and depth_sigma (:196-226),
+   quadratic_fit (:401-491: the window about the rounded pixel, coordinates relative to the keypoint,
+   normal equations with the ridge quad_fit_lstsq_eps solved by an unpivoted LDL^T), backproject and
+   backprojection_cov (:371-399) and the assembly (:547-634). h_intrinsics (host) = [fx, fy, cx, cy];
+   h_cfg (host) = GC_CAMFEAT_CFG_LEN values. Outputs (device, caller-allocated), laid out as
+   gc_camera_measurement_batch reads its feature arguments: d_uv (M, 2), d_Lambda_c, d_theta_c,
+   d_weight, d_kappa (M), d_mu_app (M, 3; the normal over (norm + 1e-12), 0 without a fit),
+   d_has_mu_app (uint8; the rows with a fit), d_color (M, 3), d_has_color (uint8), d_xyz (M, 3),
+   d_cov_xyz (M, 3, 3; a non-finite covariance is replaced by 1e6 I, :1600-1601) and d_aux
+   (M, GC_CAMFEAT_AUX). A keypoint without a valid depth gets xyz 0, invalid_cov_inflate I, weight 0
+   and Lambda_c = theta_c = 0. One wavefront per keypoint, every sum in a fixed order, no atomics: the
+   outputs are bitwise reproducible. No wait. GC_ERR_ARG for M outside [0, 4096], H or W < 1 or
+   H W > 2^26, max(1, hex_radius) or max(1, quad_fit_radius) outside [1, 3], quad_fit_min_points < 1,
+   an unknown mode or model code, non-finite intrinsics or fx, fy = 0, NaN in h_cfg, or NULL pointers
+   (d_rgb excepted). */
+int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* d_depth, const uint8_t* d_rgb,
+                                int64_t M, const double* d_kp, const double* h_intrinsics, const double* h_cfg,
+                                double* d_uv, double* d_Lambda_c, double* d_theta_c, double* d_weight,
+                                double* d_kappa, double* d_mu_app, uint8_t* d_has_mu_app, double* d_color,
+                                uint8_t* d_has_color, double* d_xyz, double* d_cov_xyz, double* d_aux);
+
 /* measurement_batch_from_camera_splats (backend/structures/measurement_batch.py:165-259): rows
    [0, min(N, n_feat)) of a fresh batch from positions (N, 3), covariances (N, 3, 3), directions
    (N, 3), kappas, weights, timestamps (N) and colours (N, 3; may be NULL: grey 0.5), all on the
