@@ -10,6 +10,10 @@ namespace gc {
 size_t sort_temp_bytes(int64_t n_seg, int64_t L, bool vals);
 // keys_in -> keys_out (and vals_in -> vals_out; vals_in null: keys only) on stream st; the inputs are
 // not modified; n_seg * L < 2^32. Errors are launch errors (or hipErrorInvalidValue for the size).
+// passes (1..8): the keys are ordered by the low 8 * passes bits of their order image alone, for a caller
+// whose order is decided there (gc_keypoints.hip: integers below 2^40 held in the doubles' bit images);
+// the default orders by all 64.
 hipError_t radix_sort_pairs(hipStream_t st, const double* keys_in, double* keys_out, const uint32_t* vals_in,
-                            uint32_t* vals_out, int64_t n_seg, int64_t L, bool descending, void* temp);
+                            uint32_t* vals_out, int64_t n_seg, int64_t L, bool descending, void* temp,
+                            int passes = 8);
 }  // namespace gc

@@ -8,7 +8,8 @@
 // Key order: IEEE order of the doubles with -0.0 equal to +0.0 (the digits are taken from the usual
 // order-preserving bit image, with the two zeros given one image), equal keys in input order (every
 // pass is a stable counting sort), descending by the complemented image; the keys leave as they came
-// in (bits unchanged). Eight 8-bit passes of three kernels:
+// in (bits unchanged). Eight 8-bit passes (fewer, from the low end, for a caller whose keys are ordered
+// by their low bits alone: `passes`) of three kernels:
 //   k_sort_hist     per tile of 2048 keys: the digit histogram (LDS atomics) -> hist[seg][digit][tile]
 //   k_sort_scan     per (segment, digit): the exclusive scan of its tiles' counts in place, and the total
 //   k_sort_scatter  per tile: the digit bases (exclusive scan of the segment's totals + the tile's
@@ -165,9 +166,10 @@ size_t sort_temp_bytes(int64_t n_seg, int64_t L, bool vals) {
 }
 
 hipError_t radix_sort_pairs(hipStream_t st, const double* keys_in, double* keys_out, const uint32_t* vals_in,
-                            uint32_t* vals_out, int64_t n_seg, int64_t L, bool descending, void* temp) {
+                            uint32_t* vals_out, int64_t n_seg, int64_t L, bool descending, void* temp, int passes) {
   if (n_seg <= 0 || L <= 0) return hipSuccess;
   if (n_seg * L >= ((int64_t)1 << 32) || L >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
+  if (passes < 1 || passes > kSortPasses) return hipErrorInvalidValue;
   const int64_t nbs = (L + kSortTile - 1) / kSortTile;
   const bool vals = vals_in != nullptr;
   Carver c{(char*)temp};
@@ -175,13 +177,15 @@ hipError_t radix_sort_pairs(hipStream_t st, const double* keys_in, double* keys_
   uint64_t* kt = t.kt;
   uint32_t *vt = t.vt, *hist = t.hist, *totals = t.totals;
   const unsigned tiles = (unsigned)(n_seg * nbs), scans = (unsigned)(n_seg * kSortDigits);
-  for (int pass = 0; pass < kSortPasses; ++pass) {
+  for (int pass = 0; pass < passes; ++pass) {
     const int shift = 8 * pass;
-    // even passes into the temporary buffers, odd ones into the outputs: the eighth pass ends there
-    const uint64_t* ks = pass == 0 ? (const uint64_t*)keys_in : ((pass & 1) ? kt : (const uint64_t*)keys_out);
-    const uint32_t* vs = pass == 0 ? vals_in : ((pass & 1) ? vt : vals_out);
-    uint64_t* kd = (pass & 1) ? (uint64_t*)keys_out : kt;
-    uint32_t* vd = (pass & 1) ? vals_out : vt;
+    // the passes alternate between the temporary buffers and the outputs so that the last one ends in the
+    // outputs (of eight: even passes into the temporaries, odd ones into the outputs)
+    const bool to_out = ((passes - 1 - pass) & 1) == 0;
+    const uint64_t* ks = pass == 0 ? (const uint64_t*)keys_in : (to_out ? kt : (const uint64_t*)keys_out);
+    const uint32_t* vs = pass == 0 ? vals_in : (to_out ? vt : vals_out);
+    uint64_t* kd = to_out ? (uint64_t*)keys_out : kt;
+    uint32_t* vd = to_out ? vals_out : vt;
     if (descending) hipLaunchKernelGGL(k_sort_hist<true>, dim3(tiles), dim3(kSortWG), 0, st, ks, L, (int)nbs, shift, hist);
     else hipLaunchKernelGGL(k_sort_hist<false>, dim3(tiles), dim3(kSortWG), 0, st, ks, L, (int)nbs, shift, hist);
     hipLaunchKernelGGL(k_sort_scan, dim3(scans), dim3(kSortWG), 0, st, hist, (int)nbs, totals);

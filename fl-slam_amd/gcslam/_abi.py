@@ -168,6 +168,9 @@ SIGNATURES = {
                                                                                     _i32, _f64] + [_vp] * 14,
     "gc_measurement_batch_from_camera_splats": [_vp, _i64] + [_vp] * 7 + [_i32, _i32, _i32, _f64] + [_vp] * 9,
     "gc_camera_features_lift": [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp] + [_vp] * 12,
+    "gc_keypoints_plan": [_i32, _i32, _vp, _vp, _vp, _vp],
+    "gc_keypoints_resize_table": [_i64, _i64, _vp, _vp],
+    "gc_keypoints_detect": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "gc_renderable_batch_from_view": [_vp, _vp, _f64, _vp, C.POINTER(C.c_int64)],
     "gc_bev_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gc_render_ewa_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp],
@@ -224,6 +227,10 @@ GC_CAM_MAX_QUERIES = 4096
 GC_CAM_MAX_FIT_POINTS = 256     # gc_camsplat.hip: one fitted point per thread
 GC_CAMFEAT_CFG_LEN = 24
 GC_CAMFEAT_AUX = 6
+GC_KP_CFG_LEN = 6
+GC_KP_MAX_LEVELS = 16
+GC_KP_PLAN_ROW = 5
+GC_KP_COUNTS_LEN = 49
 
 
 class PipelineDims(C.Structure):

@@ -4,8 +4,9 @@ and what the backend makes of its message (backend/backend_node.py:1589-1645), a
 camera_measurement_batch takes. Per keypoint: a robust depth sample (:228-348), the Student-t
 variance inflation (:350-369), the quadratic surface fit with its normal, Gaussian curvature and
 smaller Hessian eigenvalue (:401-491), the closed-form backprojection covariance (:371-399), the vMF
-concentration, the depth natural parameters and the colour (:547-634). ORB detection stays the
-caller's: keypoints (u, v, response) are the input, as the LiDAR points are the surfel extractor's.
+concentration, the depth natural parameters and the colour (:547-634). Keypoints (u, v, response) are
+the input, as the LiDAR points are the surfel extractor's: the caller's own detector's on the host, or
+the table detect_keypoints (keypoint_detector.py) leaves in HBM.
 All arithmetic runs in libgcslam (csrc/gc_camfeat.hip); every argument error is raised here before a
 device is asked for."""
 
@@ -19,6 +20,7 @@ import numpy as np
 
 from .. import _abi
 from .camera_splats import CameraFeatures, DeviceCameraFeatures, PinholeIntrinsics, _intr_vector, _n_rows
+from .keypoint_detector import DeviceKeypoints
 
 DEPTH_SAMPLE_MODES = ("nearest", "median3", "median5", "hex")  # the codes 0..3 of the GC_CAMFEAT_CFG_LEN vector
 DEPTH_MODELS = ("linear", "quadratic")                         # the codes 0, 1
@@ -139,8 +141,10 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
     depth_scale and rgb (H, W, 3) uint8 or None (no colours: has_color False, color 0) are host arrays
     or DeviceArrays (float32 / uint8); a host depth of another float or integer dtype is converted to
     float32 first (the node always receives 32FC1). keypoints_uv (M, 2) and responses (M) are host
-    arrays; more than config.max_features of them are cut with select_keypoints first. intrinsics: a
-    PinholeIntrinsics or [fx, fy, cx, cy].
+    arrays; more than config.max_features of them are cut with select_keypoints first. keypoints_uv may
+    instead be the DeviceKeypoints of detect_keypoints(..., device_out=True) with responses None: the
+    first count rows of its (u, v, response) table are read in HBM, and a count above
+    config.max_features is a ValueError. intrinsics: a PinholeIntrinsics or [fx, fy, cx, cy].
 
     Returns CameraFeatures with aux (M, GC_CAMFEAT_AUX; AUX_NAMES) set; with device_out a
     DeviceCameraFeatures whose arrays stay in HBM for camera_measurement_batch. M = 0 returns the empty
@@ -176,32 +180,46 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
             rgb = np.asarray(rgb)
         if rgb.dtype != np.uint8:
             raise ValueError(f"rgb of dtype {rgb.dtype}, expected uint8 (rgb8)")
-    try:
-        uv = np.asarray(keypoints_uv, dtype=np.float64)
-        resp = np.asarray(responses, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"keypoints_uv and responses must be numeric arrays: {e}") from None
-    if uv.ndim == 1 and uv.size == 2:
-        uv = uv.reshape(1, 2)
-    m = _n_rows(uv, 2, "keypoints_uv")
-    if _n_rows(resp, 1, "responses") != m:
-        raise ValueError(f"responses holds {_n_rows(resp, 1, 'responses')} values for {m} keypoints")
-    kp = np.concatenate([uv.reshape(m, 2), resp.reshape(m, 1)], axis=1)
-    if not np.isfinite(kp).all():
-        raise ValueError("u, v and response must be finite")
-    if m > k_max:
-        kp = kp[select_keypoints(kp[:, 2], k_max)]
-        m = kp.shape[0]
+    dev_kp = keypoints_uv if isinstance(keypoints_uv, DeviceKeypoints) else None
+    if dev_kp is not None:
+        # the detector's table, read where it is: the first count rows, no download and no upload
+        if responses is not None:
+            raise ValueError("responses must be None with a DeviceKeypoints: its table carries them")
+        m = int(dev_kp.count)
+        if m > k_max:
+            raise ValueError(f"{m} device keypoints for max_features = {k_max}: detect with the same budget")
+        if m > dev_kp.table.shape[0] or dev_kp.table.shape[1:] != (3,) or dev_kp.table.dtype != np.float64:
+            raise ValueError(f"a DeviceKeypoints table of shape {dev_kp.table.shape} for count = {m}")
+    else:
+        try:
+            uv = np.asarray(keypoints_uv, dtype=np.float64)
+            resp = np.asarray(responses, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"keypoints_uv and responses must be numeric arrays: {e}") from None
+        if uv.ndim == 1 and uv.size == 2:
+            uv = uv.reshape(1, 2)
+        m = _n_rows(uv, 2, "keypoints_uv")
+        if _n_rows(resp, 1, "responses") != m:
+            raise ValueError(f"responses holds {_n_rows(resp, 1, 'responses')} values for {m} keypoints")
+        kp = np.concatenate([uv.reshape(m, 2), resp.reshape(m, 1)], axis=1)
+        if not np.isfinite(kp).all():
+            raise ValueError("u, v and response must be finite")
+        if m > k_max:
+            kp = kp[select_keypoints(kp[:, 2], k_max)]
+            m = kp.shape[0]
     if m > _abi.GC_CAM_MAX_QUERIES:
         raise ValueError(f"{m} keypoints; at most {_abi.GC_CAM_MAX_QUERIES} are supported")
     if m == 0:
         return _empty()
     if ctx is None:
         dev_in = [x for x in (depth, rgb) if isinstance(x, _abi.DeviceArray)]
-        ctx = dev_in[0].ctx if dev_in else _abi.default_context()
+        ctx = dev_in[0].ctx if dev_in else (dev_kp.table.ctx if dev_kp is not None else _abi.default_context())
     d_depth = _abi.device_input(ctx, depth, np.float32, (H, W))
     d_rgb = _abi.device_input(ctx, rgb, np.uint8, (H, W, 3)) if rgb is not None else None
-    (d_kp,) = _abi.upload_many(ctx, [np.ascontiguousarray(kp)])
+    if dev_kp is not None:
+        d_kp = dev_kp.table
+    else:
+        (d_kp,) = _abi.upload_many(ctx, [np.ascontiguousarray(kp)])
     out = _abi.alloc_many(ctx, [((m,) + shp, dt) for _, shp, dt in _OUT])
     _abi.call("gc_camera_features_lift", ctx.handle, H, W, d_depth.ptr, d_rgb.ptr if d_rgb is not None else None, m,
               d_kp.ptr, h_k.ctypes.data, h_cfg.ctypes.data, *[o.ptr for o in out], ctx=ctx)

@@ -1217,6 +1217,54 @@ int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* 
                                 double* d_kappa, double* d_mu_app, uint8_t* d_has_mu_app, double* d_color,
                                 uint8_t* d_has_color, double* d_xyz, double* d_cov_xyz, double* d_aux);
 
+#define GC_KP_CFG_LEN 6     /* [nfeatures, scale_factor, nlevels, edge_threshold, fast_threshold, harris_k]: the
+                               arguments of the node's cv::ORB::create (src/visual_feature_node.cpp:149-158;
+                               512, 1.2, 8, 31, 20) and Harris's k (0.04) */
+#define GC_KP_MAX_LEVELS 16
+#define GC_KP_PLAN_ROW 5    /* per level: W_l, H_l, the quota n_l, the candidate capacity
+                               ceil(W_l / 2) ceil(H_l / 2), the level's byte offset in the pyramid */
+#define GC_KP_COUNTS_LEN 49 /* per level l < GC_KP_MAX_LEVELS [3 l .. 3 l + 2]: the corners after non-maximum
+                               suppression, after the border, and kept; [48]: the total */
+/* The plan of the keypoint detector for an H x W image (host only; build-defined, DESIGN.md §4 "Keypoint
+   detector"; the detector half of the node's ORB, src/visual_feature_node.cpp:149-158, :512-535):
+   s_l = (double)(float)pow((double)(float)scale_factor, l), W_l = rint(W / s_l) and H_l = rint(H / s_l)
+   (halves to even, at least 1), the quotas n_l of ORB's geometric split (the last level takes what is
+   left), the candidate capacities and the levels' byte offsets in the pyramid (each level row-major
+   uint8 on a 256-byte boundary). h_levels (GC_KP_MAX_LEVELS, GC_KP_PLAN_ROW) and h_scales
+   (GC_KP_MAX_LEVELS), zero from nlevels on; h_bytes = [pyramid bytes, workspace bytes (the context's
+   scratch a call carves)]. GC_ERR_ARG as gc_keypoints_detect. */
+int32_t gc_keypoints_plan(int32_t H, int32_t W, const double* h_cfg, int64_t* h_levels, double* h_scales,
+                          int64_t* h_bytes);
+
+/* Test entry (host only), in the manner of gc_test_bounded_wait: the index and weight table of one axis
+   of the detector's 8-bit bilinear resize n_src -> n_dst (build-defined; src/visual_feature_node.cpp:149-158,
+   :512-535 run cv::ORB's pyramid): per destination j, f = (j + 0.5) n_src / n_dst - 0.5, h_i0 = floor(f),
+   h_w1 = rint((f - h_i0) 2048), clamped to the source ((0, 0) below, (n_src - 1, 0) from the last sample
+   on). GC_ERR_ARG for a size outside [1, 2^26] or NULL pointers. */
+int32_t gc_keypoints_resize_table(int64_t n_src, int64_t n_dst, int32_t* h_i0, int32_t* h_w1);
+
+/* The detector half of the node's ORB (src/visual_feature_node.cpp:149-158, :512-535; cv::ORB with
+   HARRIS_SCORE) on the device, build-defined: it follows the published algorithms and DESIGN.md §4
+   "Keypoint detector" states every step; it was not checked against OpenCV and does not claim its bits.
+   d_image (device, uint8, H x W x channels; channels 3: rgb8, 1: grey) -> grey (4899 R + 9617 G +
+   1868 B + 8192) >> 14 -> nlevels pyramid levels in d_pyramid (gc_keypoints_plan's bytes and offsets;
+   8-bit bilinear, 11-bit weights) -> per level FAST-9/16 with score max-min-arc - 1, strict 3 x 3
+   non-maximum suppression, the border edge_threshold, the 2 n_l best by (score descending, raster index
+   ascending), their 7 x 7 Harris responses in f64, the n_l best by (response descending, raster index
+   ascending). Outputs (device, caller-allocated): d_kp (nfeatures, 3) = (x s_l, y s_l, response) f64,
+   levels ascending; d_meta (nfeatures, 4) int32 = (level, x, y, FAST score); d_counts
+   (GC_KP_COUNTS_LEN int32). Rows from the total on are zero. No angle, size, descriptor or blur.
+   Integer arithmetic and seven f64 operations per response: bitwise reproducible and independent of
+   the order the candidates are found in. No wait: the resize tables go up in one staged upload while
+   they fit 512 KiB (33 KB at 640 x 480), else per level, and only a level whose own tables exceed
+   512 KiB waits for its upload. GC_ERR_ARG before any launch for H or W < 1 or H W > 2^26, channels not 1 or 3,
+   nfeatures outside [1, 4096], nlevels outside [1, 16], a scale_factor not finite or <= 1 as float32,
+   fast_threshold outside [1, 254], edge_threshold outside [4, 1024] (4 keeps the Harris reads inside
+   the image), a non-finite harris_k, a non-integer count, or NULL pointers. */
+int32_t gc_keypoints_detect(gc_ctx* ctx, int32_t H, int32_t W, int32_t channels, const uint8_t* d_image,
+                            const double* h_cfg, uint8_t* d_pyramid, double* d_kp, int32_t* d_meta,
+                            int32_t* d_counts);
+
 /* measurement_batch_from_camera_splats (backend/structures/measurement_batch.py:165-259): rows
    [0, min(N, n_feat)) of a fresh batch from positions (N, 3), covariances (N, 3, 3), directions
    (N, 3), kappas, weights, timestamps (N) and colours (N, 3; may be NULL: grey 0.5), all on the
