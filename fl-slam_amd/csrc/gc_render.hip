@@ -31,16 +31,14 @@
 #include "gc_internal.h"
 #include "gc_math.h"
 #include "gc_mapslot.h"
+#include "gc_renderdev.h"
 #include "gc_sort.h"
 
 namespace gc {
 namespace {
 
-constexpr int kRdT = 256;             // threads of every workgroup here
-constexpr int kRdMaxTile = 32;        // rendering.py:267, :320: tile_size is clamped to [1, 32]
-constexpr int kRdMaxCap = 256;        // splat records one raster step holds in LDS
+// kRdT, kRdMaxTile, kRdMaxCap and kRdMaxViews (9 doubles per view here): gc_renderdev.h
 constexpr int kRdRec = 10;            // a record: mean 2, Sigma^-1 4, alpha 1, rgb 3
-constexpr int kRdMaxViews = 32;           // the views travel by value as a kernel argument (9 doubles each)
 
 // ------------------------------------------------------------------------------------------------
 // renderable batch
@@ -216,20 +214,7 @@ __global__ __launch_bounds__(kRdT) void k_bev_prep(int64_t n, int n_views, gc_re
   const double raw = 1.0 / (1.0 + exp(-c.gamma * (c.logdet0 - logdet)));
   const double alpha = c.alpha_min + (1.0 - c.alpha_min) * raw;
   // vmf_shading_multi_lobe (:135-159): pi_b uniform, no intensity, mu_app = eta_b, kappa_app = |eta_b|
-  const double nv = sqrt(vd[0] * vd[0] + vd[1] * vd[1] + vd[2] * vd[2]) + 1e-12;
-  const double v0 = vd[0] / nv, v1 = vd[1] / nv, v2 = vd[2] / nv;
-  const int L = b.n_lobes;
-  const double pi_b = 1.0 / (double)L;
-  double s = 0.0, kappa_sum = 0.0;
-  for (int l = 0; l < L; ++l) {
-    const double e0 = b.eta[(i * L + l) * 3], e1 = b.eta[(i * L + l) * 3 + 1], e2 = b.eta[(i * L + l) * 3 + 2];
-    const double kap = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-    const double nm = kap + 1e-12;
-    const double dot = (e0 / nm) * v0 + (e1 / nm) * v1 + (e2 / nm) * v2;
-    s += pi_b * exp(kap * (dot - 1.0));
-    kappa_sum += kap;
-  }
-  s = s / (1.0 + kappa_sum / (double)L);
+  const double s = rd_vmf_shading(b.eta, i, b.n_lobes, vd);
   // fbm at the splat's world (x, y) and the colour modulation (:333-340)
   const double f = rd_fbm(mu[0], mu[1], c.octaves, c.gain, c.seed);
   const double mod = (1.0 - c.s_f) + c.s_f * f;
@@ -253,12 +238,6 @@ __global__ __launch_bounds__(kRdT) void k_bev_prep(int64_t n, int n_views, gc_re
 // tile binning (rendering.py:252-289)
 // ------------------------------------------------------------------------------------------------
 
-struct TileGrid {
-  int tiles_x, T;  // tiles per row and per view
-  int ts;          // tile_size
-  int oy0, ox0;    // origin of tile 0
-};
-
 // The binning key of splat i for segment seg (a (view, tile)): dist_sq to the tile centre, +inf where
 // the four-sided bbox test rejects it (:283, the reference's strict inequalities).
 GC_DEV double rd_bin_key(int64_t n, int64_t seg, const TileGrid& G, const double* means, const double* Sinv,
@@ -268,9 +247,7 @@ GC_DEV double rd_bin_key(int64_t n, int64_t seg, const TileGrid& G, const double
   const double ox = (double)(G.ox0 + (t % G.tiles_x) * G.ts), oy = (double)(G.oy0 + (t / G.tiles_x) * G.ts);
   const double* Si = Sinv + 4 * (v * n + i);
   // the smaller eigenvalue of the symmetric 2 x 2 (eigvalsh reads the lower triangle)
-  const double a = Si[0], b = Si[2], d = Si[3];
-  const double hd = 0.5 * (a - d);
-  const double lam = fmax(0.5 * (a + d) - sqrt(hd * hd + b * b), eps);
+  const double lam = fmax(rd_eig_min2(Si[0], Si[2], Si[3]), eps);
   const double r = 2.0 / sqrt(lam);
   const double mx = means[2 * (v * n + i)], my = means[2 * (v * n + i) + 1];
   const double x_max = ox + (double)G.ts, y_max = oy + (double)G.ts;
@@ -281,72 +258,21 @@ GC_DEV double rd_bin_key(int64_t n, int64_t seg, const TileGrid& G, const double
   return rejected ? HUGE_VAL : dist_sq;
 }
 
-// One workgroup per (view, tile), cap <= kRdMaxCap: the splats are scanned 256 at a time in index
-// order, the survivors (finite keys) appended to an LDS list in that order (ballot ranks, the waves'
-// counts through LDS), and whenever the list holds more than cap entries it is cut back to its cap
-// smallest by (dist_sq, index): every entry counts the entries below it, which is its place in the
-// sorted list. The cap smallest of a prefix's cap smallest and the rest are the cap smallest of all,
-// so the result is the first cap of the stable sort by dist_sq, whatever the chunking.
-constexpr int kBinBuf = kRdMaxCap + kRdT;
+// One workgroup per (view, tile), cap <= kRdMaxCap: the cap smallest survivors by (dist_sq, index)
+// through the LDS selection of gc_renderdev.h (rd_select_smallest), the key being rd_bin_key.
+struct BevKey {
+  int64_t n, seg;
+  TileGrid G;
+  const double *means, *Sinv;
+  double eps;
+  GC_DEV double operator()(int64_t i) const { return rd_bin_key(n, seg, G, means, Sinv, eps, i); }
+};
 
 __global__ __launch_bounds__(kRdT) void k_bin_select(int64_t n, TileGrid G, const double* means, const double* Sinv,
                                                      double eps, int cap, int32_t* counts, int32_t* indices) {
-  __shared__ double cd[kBinBuf], td[kRdMaxCap];
-  __shared__ int32_t ci[kBinBuf], ti[kRdMaxCap];
-  __shared__ int wcnt[kRdT / 64];
   const int64_t seg = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  int count = 0;  // the same in every thread
-  // the list cut back to min(count, cap) entries, sorted
-  auto cut = [&]() {
-    const int keep = count < cap ? count : cap;
-    for (int e = tid; e < count; e += kRdT) {
-      const double de = cd[e];
-      const int32_t ie = ci[e];
-      int r = 0;
-      for (int j = 0; j < count; ++j) {
-        const double dj = cd[j];
-        r += (dj < de || (dj == de && ci[j] < ie)) ? 1 : 0;
-      }
-      if (r < keep) {
-        td[r] = de;
-        ti[r] = ie;
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < keep; e += kRdT) {
-      cd[e] = td[e];
-      ci[e] = ti[e];
-    }
-    __syncthreads();
-    count = keep;
-  };
-  for (int64_t base = 0; base < n; base += kRdT) {
-    const int64_t i = base + tid;
-    double d = HUGE_VAL;
-    if (i < n) d = rd_bin_key(n, seg, G, means, Sinv, eps, i);
-    const bool in = d < HUGE_VAL;
-    const unsigned long long m = __ballot(in);
-    if (lane == 0) wcnt[w] = (int)__popcll(m);
-    __syncthreads();
-    int pre = 0, total = 0;
-#pragma unroll
-    for (int u = 0; u < kRdT / 64; ++u) {
-      pre += u < w ? wcnt[u] : 0;
-      total += wcnt[u];
-    }
-    if (in) {
-      const int at = count + pre + (int)__popcll(m & ((1ull << lane) - 1ull));
-      cd[at] = d;
-      ci[at] = (int32_t)i;
-    }
-    __syncthreads();
-    count += total;
-    if (count > cap) cut();
-  }
-  cut();
-  for (int c = tid; c < cap; c += kRdT) indices[seg * cap + c] = c < count ? ci[c] : -1;
-  if (tid == 0) counts[seg] = count;
+  const BevKey key{n, seg, G, means, Sinv, eps};
+  rd_select_smallest<false>(n, seg, key, cap, counts, nullptr, indices);
 }
 
 // The same through the library's sort, for a cap above kRdMaxCap (the one-tile entry only): the keys of

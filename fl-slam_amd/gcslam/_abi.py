@@ -177,6 +177,8 @@ SIGNATURES = {
     "gc_splat_indices_for_tile": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _vp, C.POINTER(C.c_int32)],
     "gc_render_tile_ewa": [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _f64, _vp],
     "gc_fbm_at_positions": [_vp, _i64, _vp, _i32, _f64, _i64, _vp],
+    "gc_camera_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
+    "gc_render_depth_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp] + [_vp] * 7,
 }
 
 GC_PCFG_LEN = 22

@@ -11,8 +11,14 @@
   no wait between them. The reference has the pieces but never composes them; the composition is this
   build's and is declared in DESIGN.md §4.
 
-All arithmetic runs in libgcslam (csrc/gc_render.hip); every argument error is raised here before a
-device is asked for."""
+- CameraViewConfig, camera_from_world, camera_splat_prep, render_depth_tiles, render_map_camera: the
+  map seen through a pinhole at a camera pose, what tools/view_splat_jaxsplat.py renders from the exported
+  map and the last trajectory pose: perspective splats, per-tile lists in depth order, front-to-back
+  compositing, with a depth image beside the colour image. The raster the viewer leaves to
+  jaxsplat.render_v2 is this build's and is declared in DESIGN.md §4 ("Camera view").
+
+All arithmetic runs in libgcslam (csrc/gc_render.hip, csrc/gc_camrender.hip); every argument error is
+raised here before a device is asked for."""
 
 from __future__ import annotations
 
@@ -26,9 +32,11 @@ import numpy as np
 from . import _abi
 from .association import DeviceMapView, extract_atlas_map_view
 from .constants import GC_EPS_LIFT
+from .ops.camera_splats import PinholeIntrinsics
 from .primitive_map import DevicePrimitiveMap
 
 GC_BEV_CFG_LEN = 11
+GC_CAMVIEW_CFG_LEN = 13
 GC_RENDER_MAX_VIEWS = 32   # gc_render.hip: the views travel as one kernel argument
 GC_RENDER_MAX_CAP = 256    # gc_render.hip: splat records one tile holds in LDS
 GC_RENDER_MAX_TILE = 32    # rendering.py:267
@@ -357,6 +365,200 @@ def render_map_bev(batch_or_map: Union[DeviceRenderableBatch, RenderablePrimitiv
     images, counts, indices = _abi.download_many([dev["images"], dev["tile_counts"], dev["tile_indices"]])
     return BevRender(images=images.copy(), tile_counts=counts.copy(), tile_indices=indices.copy(),
                      device=dict(dev, **splats))
+
+
+# ---------------------------------------------------------------------------------------------
+# the camera view: perspective splats, depth-ordered lists, front-to-back compositing
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class CameraViewConfig:
+    """The camera view's raster ("Camera view"). alpha_floor is the viewer's clip of
+    mass / m_max (view_splat_jaxsplat.py:111); the rest is the build's."""
+    tile_size: int = 16
+    max_splats_per_tile: int = 256
+    near: float = 0.2
+    far: float = 100.0
+    lowpass_px2: float = 0.3
+    radius_sigma: float = 3.0
+    alpha_floor: float = 0.01
+    alpha_max: float = 0.99
+    alpha_skip: float = 1.0 / 255.0
+    t_stop: float = 1e-4
+    background: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    shade: bool = True
+    eps: float = 1e-12
+
+
+@dataclass
+class CameraRender:
+    """render_map_camera's result: images (n_views, H, W, 3), alpha and depth (n_views, H, W), n_contrib
+    (n_views, H, W) int32, the per-tile lists tile_counts and tile_survivors (n_views, T; the survivors
+    before the cut at max_splats_per_tile), tile_indices (n_views, T, cap; -1 past the count), and
+    `device`, the DeviceArrays behind them and the 2D splats."""
+    images: np.ndarray
+    alpha: np.ndarray
+    depth: np.ndarray
+    n_contrib: np.ndarray
+    tile_counts: np.ndarray
+    tile_survivors: np.ndarray
+    tile_indices: np.ndarray
+    device: Dict[str, _abi.DeviceArray]
+
+
+class _CamSplatStruct(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("means_px", "Sigmas_inv", "depths", "radii", "alphas", "colors", "valid")]
+
+
+def camera_from_world(pose, R_base_camera=None, t_base_camera=None, *, ctx=None) -> np.ndarray:
+    """T_cw = inv(T_wb T_bc) (4, 4): what the viewer takes as its camera (view_splat_jaxsplat.py:103,
+    camera-at-body: T_bc = I, the default). pose is the body pose in the world, either the 6-vector
+    (translation, rotation vector; the rotation through ops/se3.so3_exp, on the device) or a 4 x 4
+    T_wb, which needs no device."""
+    p = np.asarray(pose, np.float64)
+    Rbc = np.eye(3) if R_base_camera is None else np.asarray(R_base_camera, np.float64)
+    tbc = np.zeros(3) if t_base_camera is None else np.asarray(t_base_camera, np.float64).reshape(-1)
+    if Rbc.shape != (3, 3) or tbc.shape != (3,):
+        raise ValueError(f"R_base_camera of shape {Rbc.shape} and t_base_camera of shape {tbc.shape}: expected (3, 3), (3,)")
+    if p.shape not in ((6,), (4, 4)):
+        raise ValueError(f"pose of shape {p.shape}: expected (6,) or (4, 4)")
+    if not (np.isfinite(p).all() and np.isfinite(Rbc).all() and np.isfinite(tbc).all()):
+        raise ValueError("the pose and the extrinsics must be finite")
+    if p.shape == (4, 4):
+        if not np.array_equal(p[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("the bottom row of T_wb must be (0, 0, 0, 1)")
+        Rwb, twb = p[:3, :3], p[:3, 3]
+    else:
+        from .ops import se3
+        Rwb, twb = se3.so3_exp(p[3:], ctx=ctx), p[:3]
+    Rwc, twc = Rwb @ Rbc, Rwb @ tbc + twb
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = Rwc.T, -Rwc.T @ twc
+    return T
+
+
+def _cam_cfg_vector(cfg: CameraViewConfig) -> np.ndarray:
+    bg = np.asarray(cfg.background, np.float64).reshape(-1)
+    if bg.shape != (3,):
+        raise ValueError(f"background must hold 3 values, got {cfg.background!r}")
+    h = np.array([cfg.near, cfg.far, cfg.lowpass_px2, cfg.radius_sigma, cfg.alpha_floor, cfg.alpha_max, cfg.alpha_skip,
+                  cfg.t_stop, bg[0], bg[1], bg[2], 1.0 if cfg.shade else 0.0, cfg.eps], np.float64)
+    assert h.shape[0] == GC_CAMVIEW_CFG_LEN
+    if not np.isfinite(h).all():
+        raise ValueError("the camera view configuration must be finite")
+    if not (cfg.near > 0.0 and cfg.far > cfg.near):
+        raise ValueError(f"near must be > 0 and far > near, got near = {cfg.near}, far = {cfg.far}")
+    if not 0.0 < cfg.alpha_max <= 1.0:
+        raise ValueError(f"alpha_max must be in (0, 1], got {cfg.alpha_max}")
+    return h
+
+
+def _cam_views(intrinsics, T_cw) -> Tuple[np.ndarray, np.ndarray]:
+    """(T_cw (n_views, 4, 4), intrinsics (n_views, 4) as fx fy cx cy), checked."""
+    T = np.ascontiguousarray(T_cw, np.float64)
+    if T.ndim == 2:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4):
+        raise ValueError(f"T_cw of shape {np.shape(T_cw)}: expected (4, 4) or (n_views, 4, 4)")
+    nv = T.shape[0]
+    if not 1 <= nv <= GC_RENDER_MAX_VIEWS:
+        raise ValueError(f"{nv} views; between 1 and {GC_RENDER_MAX_VIEWS} are supported")
+    ks = [intrinsics] if isinstance(intrinsics, PinholeIntrinsics) else list(intrinsics)
+    if len(ks) != nv:
+        raise ValueError(f"{len(ks)} intrinsics for {nv} views")
+    K = np.array([[k.fx, k.fy, k.cx, k.cy] for k in ks], np.float64).reshape(nv, 4)
+    if not (np.isfinite(T).all() and np.isfinite(K).all()):
+        raise ValueError("T_cw and the intrinsics must be finite")
+    if not (K[:, :2] > 0.0).all():
+        raise ValueError("fx and fy must be > 0")
+    if not (T[:, 3] == np.array([0.0, 0.0, 0.0, 1.0])).all():
+        raise ValueError("the bottom row of T_cw must be (0, 0, 0, 1)")
+    R = T[:, :3, :3]
+    if np.max(np.abs(np.swapaxes(R, 1, 2) @ R - np.eye(3))) > 1e-9:
+        raise ValueError("the 3 x 3 block of T_cw must be a rotation (max |R^T R - I| <= 1e-9)")
+    return T, K
+
+
+def _check_camera_args(intrinsics, T_cw, height, width, cfg: CameraViewConfig, n: int):
+    _check_raster_args(cfg.tile_size, height, width, cfg.max_splats_per_tile, n)
+    h_cfg = _cam_cfg_vector(cfg)
+    T, K = _cam_views(intrinsics, T_cw)
+    tiles = (int(height) // int(cfg.tile_size)) * (int(width) // int(cfg.tile_size))
+    if T.shape[0] * tiles * n >= 1 << 32:
+        raise ValueError(f"n_views * tiles * n = {T.shape[0] * tiles * n} must be below 2^32")
+    return h_cfg, T, K
+
+
+def camera_splat_prep(batch: DeviceRenderableBatch, intrinsics, T_cw, height: int, width: int,
+                      cfg: Optional[CameraViewConfig] = None) -> Dict[str, _abi.DeviceArray]:
+    """The 2D splats of the batch's `count` rows for every camera view (gc_camera_splat_prep,
+    include/gcslam.h): means_px (n_views, n, 2), Sigmas_inv (n_views, n, 2, 2), depths and radii
+    (n_views, n), alphas (n), colors (n_views, n, 3), valid (n_views, n) uint8. intrinsics: a
+    PinholeIntrinsics or one per view; T_cw (4, 4) or (n_views, 4, 4) (camera_from_world). No wait."""
+    cfg = cfg or CameraViewConfig()
+    n, ctx = batch.count, batch.ctx
+    h_cfg, T, K = _check_camera_args(intrinsics, T_cw, height, width, cfg, n)
+    nv = T.shape[0]
+    names = [k for k, _ in _CamSplatStruct._fields_]
+    specs = dict(means_px=((nv, n, 2), np.float64), Sigmas_inv=((nv, n, 2, 2), np.float64), depths=((nv, n), np.float64),
+                 radii=((nv, n), np.float64), alphas=((n,), np.float64), colors=((nv, n, 3), np.float64),
+                 valid=((nv, n), np.uint8))
+    out = dict(zip(names, _abi.alloc_many(ctx, [specs[k] for k in names])))
+    st = _CamSplatStruct(*[out[k].ptr for k in names])
+    _abi.call("gc_camera_splat_prep", ctx.handle, C.byref(batch.struct), n, nv, T.ctypes.data, K.ctypes.data, int(height),
+              int(width), h_cfg.ctypes.data, C.byref(st), ctx=ctx)
+    return out
+
+
+def render_depth_tiles(splats: Dict[str, _abi.DeviceArray], height: int, width: int,
+                       cfg: Optional[CameraViewConfig] = None, *, ctx=None) -> Dict[str, _abi.DeviceArray]:
+    """The depth-ordered tile lists and the front-to-back composite of camera splats
+    (gc_render_depth_tiles): images (n_views, H, W, 3), alpha, depth (n_views, H, W), n_contrib
+    (n_views, H, W) int32, tile_counts, tile_survivors (n_views, T), tile_indices (n_views, T, cap),
+    all on the device. No wait."""
+    cfg = cfg or CameraViewConfig()
+    nv, n = splats["depths"].shape
+    _check_raster_args(cfg.tile_size, height, width, cfg.max_splats_per_tile, n)
+    h_cfg = _cam_cfg_vector(cfg)
+    if not 1 <= nv <= GC_RENDER_MAX_VIEWS:
+        raise ValueError(f"{nv} views; between 1 and {GC_RENDER_MAX_VIEWS} are supported")
+    ts, H, W, cap = int(cfg.tile_size), int(height), int(width), int(cfg.max_splats_per_tile)
+    T = (H // ts) * (W // ts)
+    if nv * T * n >= 1 << 32:
+        raise ValueError(f"n_views * tiles * n = {nv * T * n} must be below 2^32")
+    ctx = ctx or splats["depths"].ctx
+    names = ("images", "alpha", "depth", "n_contrib", "tile_counts", "tile_survivors", "tile_indices")
+    arrays = _abi.alloc_many(ctx, [((nv, H, W, 3), np.float64), ((nv, H, W), np.float64), ((nv, H, W), np.float64),
+                                   ((nv, H, W), np.int32), ((nv, T), np.int32), ((nv, T), np.int32),
+                                   ((nv, T, cap), np.int32)])
+    st = _CamSplatStruct(*[splats[k].ptr for k, _ in _CamSplatStruct._fields_])
+    _abi.call("gc_render_depth_tiles", ctx.handle, nv, n, C.byref(st), H, W, ts, cap, h_cfg.ctypes.data,
+              *[a.ptr for a in arrays], ctx=ctx)
+    return dict(zip(names, arrays))
+
+
+def render_map_camera(batch_or_map: Union[DeviceRenderableBatch, RenderablePrimitiveBatch, DevicePrimitiveMap],
+                      intrinsics, T_cw, height: int, width: int, cfg: Optional[CameraViewConfig] = None, *,
+                      ctx=None) -> CameraRender:
+    """The map through a pinhole at T_cw (camera_from_world of the pose): colour, coverage and depth
+    images of a renderable batch (or of a map: publish_renderable first), one per view. The two device
+    calls run with no wait between them and everything is downloaded once at the end. ValueError
+    before a device is asked for: see DESIGN.md §4 for the list."""
+    cfg = cfg or CameraViewConfig()
+    _check_camera_args(intrinsics, T_cw, height, width, cfg, 0)
+    if isinstance(batch_or_map, DevicePrimitiveMap):
+        batch = publish_renderable(batch_or_map)
+    elif isinstance(batch_or_map, DeviceRenderableBatch):
+        batch = batch_or_map
+    elif isinstance(batch_or_map, RenderablePrimitiveBatch):
+        batch = DeviceRenderableBatch.from_host(ctx or _abi.default_context(), batch_or_map)
+    else:
+        raise ValueError(f"cannot render a {type(batch_or_map).__name__}")
+    splats = camera_splat_prep(batch, intrinsics, T_cw, height, width, cfg)
+    dev = render_depth_tiles(splats, height, width, cfg, ctx=batch.ctx)
+    names = ("images", "alpha", "depth", "n_contrib", "tile_counts", "tile_survivors", "tile_indices")
+    host = _abi.download_many([dev[k] for k in names])
+    return CameraRender(**{k: a.copy() for k, a in zip(names, host)}, device=dict(dev, **splats))
 
 
 # ---------------------------------------------------------------------------------------------

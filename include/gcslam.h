@@ -1371,6 +1371,62 @@ int32_t gc_render_tile_ewa(gc_ctx* ctx, int64_t n, const double* d_means, const 
 int32_t gc_fbm_at_positions(gc_ctx* ctx, int64_t n, const double* d_xy, int32_t octaves, double gain, int64_t seed,
                             double* d_out);
 
+/* ------------------------------------------------------------------------------------------
+ * The camera view of the map: perspective splats, depth-ordered tile lists, front-to-back compositing
+ * (tools/view_splat_jaxsplat.py around jaxsplat.render_v2; the raster itself is this build's).
+ * ------------------------------------------------------------------------------------------ */
+#define GC_CAMVIEW_CFG_LEN 13 /* [near, far, lowpass_px2, radius_sigma, alpha_floor, alpha_max, alpha_skip, t_stop,
+                             background r, g, b, shade (0 or 1), eps] (CameraViewConfig) */
+/* The 2D splats of n_views camera views of n primitives, view-major. The caller allocates every array. */
+typedef struct gc_cam_splats {
+  double* means_px;   /* (n_views, n, 2) column, row */
+  double* Sigmas_inv; /* (n_views, n, 2, 2) */
+  double* depths;     /* (n_views, n) camera z; +inf where not valid */
+  double* radii;      /* (n_views, n) pixels */
+  double* alphas;     /* (n) the same for every view */
+  double* colors;     /* (n_views, n, 3) */
+  uint8_t* valid;     /* (n_views, n) */
+} gc_cam_splats;
+
+/* Rows [0, n) of a batch as the 2D splats of n_views pinhole views, view v with h_T_cw[v] (4, 4, row-major,
+   camera from world: p = R mu + t) and h_intrinsics[v] = (fx, fy, cx, cy) (host), for H x W images:
+   valid where p and Sigma_world are finite and near < p.z < far (strict); means_px =
+   (fx x / z + cx, fy y / z + cy); Sigma_px = sym(M Sigma M^T) + lowpass_px2 I with M = J R and
+   J = [[fx/z, 0, -fx tx/z^2], [0, fy/z, -fy ty/z^2]] at the clamped tangents
+   tx = clamp(x/z, +-1.3 max(cx, W - cx)/fx) z, ty likewise with cy, H, fy; Sigmas_inv = its closed-form
+   inverse (det = ad - b^2 of the symmetrised matrix); radii = radius_sigma sqrt(lambda_max(Sigma_px));
+   depths = p.z; colors = color * vmf_shading_multi_lobe(eta) for the unit direction from the primitive
+   to the camera centre -R^T t (shade = 0: color itself); an invalid row has depth +inf and zeros
+   elsewhere. alphas = clip(mass / m_max, alpha_floor, 1), m_max the largest positive mass of the n rows
+   (1 if none), reduced on the device (view_splat_jaxsplat.py:108-111). No wait; uses the context's
+   scratch. GC_ERR_ARG before any launch for n outside [0, 2^24], n_views outside [1, 32], n_lobes
+   outside [1, 8], H or W outside [1, 16384], fx or fy <= 0, a non-finite host value, a bottom row of
+   T_cw other than (0, 0, 0, 1), max |R^T R - I| > 1e-9, near <= 0, far <= near, alpha_max outside
+   (0, 1] or NULL pointers. n = 0 launches nothing. */
+int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_T_cw,
+                             const double* h_intrinsics, int32_t H, int32_t W, const double* h_cfg,
+                             const gc_cam_splats* out);
+
+/* The tile lists and the composited images of camera splats. Tiles as in gc_render_ewa_tiles: tile
+   (ty, tx) covers the pixels [tx ts, (tx + 1) ts) x [ty ts, (ty + 1) ts). A valid splat survives where
+   mx + r > x0, mx - r < x0 + ts, my + r > y0 and my - r < y0 + ts (all strict); a tile's list is the
+   first cap of its survivors in the order (depth ascending, index ascending): d_tile_survivors
+   (n_views, T) the number before the cut, d_tile_counts = min(survivors, cap), d_tile_indices
+   (n_views, T, cap), -1 past the count. Per pixel centre (column + 0.5, row + 0.5), from T = 1,
+   C = D = 0, n = 0, for each list entry in order: q = d^T Sigma_inv d, a = min(alpha_max,
+   alpha exp(-max(q, 0) / 2)); a < alpha_skip is skipped; else C += T a color, D += T a depth, n += 1,
+   T *= 1 - a, and the pixel stops once T < t_stop (the entry that crossed is composited). d_images
+   (n_views, H, W, 3) = C + T background, d_alpha (n_views, H, W) = 1 - T, d_depth = D / (1 - T) where
+   1 - T > eps, else 0, d_n_contrib (int32) = n. Bitwise reproducible. No wait. n = 0: empty lists from
+   memsets and the background image. GC_ERR_ARG before any launch for tile_size outside [1, 32], H or W
+   not a multiple of tile_size in [1, 16384], cap outside [1, 256], n < 0, n_views outside [1, 32], a
+   non-finite configuration value, near <= 0, far <= near, alpha_max outside (0, 1],
+   n_views * T * n >= 2^32 or NULL pointers. */
+int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_cam_splats* splats, int32_t H, int32_t W,
+                              int32_t tile_size, int32_t cap, const double* h_cfg, double* d_images, double* d_alpha,
+                              double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts, int32_t* d_tile_survivors,
+                              int32_t* d_tile_indices);
+
 #ifdef __cplusplus
 }
 #endif
