@@ -43,10 +43,10 @@ namespace gc {
 namespace {
 
 constexpr int kCfWave = 64;
-constexpr int kCfMaxRadius = 3;  // (2 r + 1)^2 <= 49 lanes
+constexpr int kCfMaxRadius = GC_CAMFEAT_MAX_RADIUS;  // (2 r + 1)^2 <= 49 lanes
 constexpr int kCfHex = 7;        // the centre and six neighbours
-constexpr int64_t kCfMaxQueries = 4096;
-constexpr int64_t kCfMaxPixels = (int64_t)1 << 26;
+constexpr int64_t kCfMaxQueries = GC_CAM_MAX_QUERIES;
+constexpr int64_t kCfMaxPixels = GC_IMAGE_MAX_PIXELS;
 constexpr double kCfEps = 1e-12;  // kEps (:34)
 static_assert((2 * kCfMaxRadius + 1) * (2 * kCfMaxRadius + 1) <= kCfWave, "one lane per window pixel");
 

@@ -40,10 +40,10 @@ namespace {
 constexpr int kCsT = 256;                      // threads per workgroup
 constexpr int kCsWaves = kCsT / 64;
 constexpr int kCsMaxNear = GC_CAM_MAX_NEAR;    // in-radius candidates a query holds in LDS
-constexpr int kCsMaxK = 256;                   // lidar_ray_plane_fit_max_points: one fitted point per thread
+constexpr int kCsMaxK = GC_CAM_MAX_FIT_POINTS;  // lidar_ray_plane_fit_max_points: one fitted point per thread
 constexpr int kCsUnroll = 8;                   // 64-point chunks in flight per wave
-constexpr int64_t kCsMaxPoints = (int64_t)1 << 22;
-constexpr int64_t kCsMaxQueries = 4096;
+constexpr int64_t kCsMaxPoints = GC_CAM_MAX_POINTS;
+constexpr int64_t kCsMaxQueries = GC_CAM_MAX_QUERIES;
 static_assert(kCsMaxK == kCsT, "the plane fit holds one selected point per thread");
 
 struct CsIntr { double fx, fy, cx, cy; };

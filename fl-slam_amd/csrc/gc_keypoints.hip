@@ -62,7 +62,7 @@ constexpr int kKpTileCap = (kKpTile / 2) * (kKpTile / 2);  // survivors a tile c
 constexpr int kKpBlock = 7;                        // the Harris block
 constexpr int kKpPad = 64;                         // words between two device counters: a 256-byte line each,
                                                    // so the tiles' atomics of different levels do not share one
-constexpr int64_t kKpMaxPixels = (int64_t)1 << 26;
+constexpr int64_t kKpMaxPixels = GC_IMAGE_MAX_PIXELS;
 constexpr int kKpRasterBits = 26, kKpScoreBits = 8, kKpLevelBits = 4;
 // The keys are 38-bit integers held in the doubles' bit images (small positive doubles order as their
 // bits do), so five 8-bit passes of the library's sort order them; an unused list entry is filled with
@@ -70,7 +70,7 @@ constexpr int kKpRasterBits = 26, kKpScoreBits = 8, kKpLevelBits = 4;
 constexpr int kKpSortPasses = (kKpRasterBits + kKpScoreBits + kKpLevelBits + 7) / 8;
 static_assert(kKpMaxPixels <= (1ll << kKpRasterBits) && kKpLevels <= (1 << kKpLevelBits), "the key's fields");
 static_assert(0x7f7f7f7f7fll >= (1ll << (kKpRasterBits + kKpScoreBits + kKpLevelBits)), "the filler sorts last");
-constexpr int kKpMaxFeatures = 4096;               // GC_CAM_MAX_QUERIES
+constexpr int kKpMaxFeatures = GC_CAM_MAX_QUERIES;  // the rows of one camera batch
 static_assert(kKpTileCap <= kKpT, "one key slot per thread is enough for a tile");
 static_assert(kKpBlock * kKpBlock <= 64, "one lane per block pixel");
 static_assert(49 * 1020 * 1020 < (1ll << 31), "the Harris sums fit int32");

@@ -320,7 +320,7 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
   const int64_t N = in->N, K = in->K, m_tile = in->m_tile;
   const int na = in->n_active, k = in->k_insert;
   GC_CHECK_ARG(ctx, N >= 1 && N <= kMuMaxRows, "N must be in [1, GC_MAP_UPDATE_MAX_ROWS]");
-  GC_CHECK_ARG(ctx, K >= 1 && K <= 64, "K must be in [1, 64]");
+  GC_CHECK_ARG(ctx, K >= 1 && K <= GC_MAP_UPDATE_MAX_K, "K must be in [1, 64]");
   GC_CHECK_ARG(ctx, na >= 1 && na <= kMuMaxActive, "n_active must be in [1, GC_MAP_UPDATE_MAX_ACTIVE]");
   GC_CHECK_ARG(ctx, m_tile >= 1 && map->m_slots % m_tile == 0, "m_tile must divide the map's slots");
   GC_CHECK_ARG(ctx, k >= 1 && k <= kMuMaxInsert && k <= N && k <= m_tile,

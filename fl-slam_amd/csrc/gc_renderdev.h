@@ -12,9 +12,9 @@
 namespace gc {
 
 constexpr int kRdT = 256;             // threads of every workgroup of the renderers
-constexpr int kRdMaxTile = 32;        // rendering.py:267, :320: tile_size is clamped to [1, 32]
-constexpr int kRdMaxCap = 256;        // splat records one raster step holds in LDS
-constexpr int kRdMaxViews = 32;       // the views travel by value as a kernel argument
+constexpr int kRdMaxTile = GC_RENDER_MAX_TILE;    // rendering.py:267, :320: tile_size is clamped to [1, 32]
+constexpr int kRdMaxCap = GC_RENDER_MAX_CAP;      // splat records one raster step holds in LDS
+constexpr int kRdMaxViews = GC_RENDER_MAX_VIEWS;  // the views travel by value as a kernel argument
 
 struct TileGrid {
   int tiles_x, T;  // tiles per row and per view

@@ -43,9 +43,9 @@ constexpr int kSfMaxGrid = 256;               // centre workgroups
 constexpr int kSfTile = 1024;                 // points per ranking tile
 constexpr int kSfRounds = kSfTile / kSfT;
 constexpr int kSfKeyBits = 14;                // cell keys are below 2^14
-constexpr int kSfMaxCells = 1 << kSfKeyBits;
-constexpr int kSfMaxOcc = 1024;               // bucket slots per cell
-constexpr int64_t kSfMaxPoints = (int64_t)1 << 22;
+constexpr int kSfMaxCells = GC_SURFEL_MAX_CELLS;
+constexpr int kSfMaxOcc = GC_SURFEL_MAX_OCCUPANTS;  // bucket slots per cell
+constexpr int64_t kSfMaxPoints = GC_SURFEL_MAX_POINTS;
 constexpr int kSfFitT = 256, kSfFitLanes = 8;  // fit: eight lanes per cell, 32 cells per workgroup
 constexpr int kSfWriteT = 256;
 constexpr int kSfRec = 18;                    // Λ_row (9) | θ (3) | κ n (3) | w | t | grey
@@ -373,6 +373,8 @@ __global__ void __launch_bounds__(kSfWriteT) k_sf_write(int n_cells, const int32
     if (t == 0) n_valid_out[0] = n_valid;
   }
 }
+
+static_assert(kSfMaxCells == 1 << kSfKeyBits, "k_sf_keys walks kSfKeyBits bits of a cell key");
 
 }  // namespace
 }  // namespace gc

@@ -1,4 +1,9 @@
-"""ctypes binding of libgcslam (include/gcslam.h).
+"""ctypes binding of libgcslam, derived from include/gcslam.h.
+
+The header is the one statement of the C-ABI: _header.py reads it at import and this module binds every
+prototype (SIGNATURES, PROTOTYPES), mirrors every struct (STRUCTS) and holds every GC_* constant as a
+module attribute. Adding an entry point means declaring it in the header and defining it in csrc/; there
+is no table here to extend. A missing or unreadable header raises RuntimeError at import.
 
 The library is loaded from this package directory (built in-tree by ``make`` in
 ``fl-slam_amd/``). There is no fallback: if the shared object is missing or no GPU is
@@ -14,231 +19,26 @@ import threading
 
 import numpy as np
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgcslam.so")
 
-GC_OK, GC_ERR_ARG, GC_ERR_RUNTIME = 0, 1, 2
-GC_BIN_STATS = 38
-GC_BIN_CERT = 8
-GC_FUSED_TAU_MIN = 3e-3
+# Every prototype, struct and GC_* constant of include/gcslam.h, read from the header at import (_header.py).
+# PROTOTYPES: name -> (argtypes, restype); SIGNATURES: name -> argtypes; STRUCTS: name -> ctypes.Structure.
+PROTOTYPES, STRUCTS, CONSTANTS = _header.load()
+SIGNATURES = {name: argtypes for name, (argtypes, _) in PROTOTYPES.items()}
+globals().update(CONSTANTS)  # _abi.GC_OK, _abi.GC_COMB_LEN, ...
+PipelineDims = STRUCTS["gc_pipeline_dims"]
 
-_vp, _dp, _i32, _i64, _u64, _f64 = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
+_vp = C.c_void_p
 _dptr = C.POINTER(C.c_double)
 
-# name -> argtypes (restype int32 unless noted). Device pointers travel as c_void_p.
-SIGNATURES = {
-    "gc_version": [],
-    "gc_device_count": [C.POINTER(C.c_int32)],
-    "gc_ctx_create": [_i32, C.POINTER(_vp)],
-    "gc_ctx_destroy": [_vp],
-    "gc_ctx_synchronize": [_vp],
-    "gc_ctx_set_wait_timeout": [_vp, _f64],
-    "gc_test_bounded_wait": [_f64, _i64, _dptr],
-    "gc_test_device_spin": [_vp, _f64],
-    "gc_test_radix_sort": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
-    "gc_buffer_alloc": [_vp, _u64, C.POINTER(_vp)],
-    "gc_buffer_free": [_vp, _vp],
-    "gc_ctx_trim": [_vp],
-    "gc_ctx_alloc_stats": [_vp, _vp],
-    "gc_buffer_upload": [_vp, _vp, _vp, _u64],
-    "gc_buffer_download": [_vp, _vp, _vp, _u64],
-    "gc_buffer_copy": [_vp, _vp, _vp, _u64],
-    "gc_buffer_memset": [_vp, _vp, _i32, _u64],
-    "gc_event_create": [_vp, C.POINTER(_vp)],
-    "gc_event_destroy": [_vp],
-    "gc_event_record": [_vp, _vp],
-    "gc_event_elapsed_ms": [_vp, _vp, C.POINTER(C.c_float)],
-    "gc_point_budget_resample": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_budget_stats": [_vp, _vp, _i64, _i64, _vp],
-    "gc_deskew_constant_twist": [_vp, _i32, _i64, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp],
-    "gc_point_directions": [_vp, _i64, _vp, _dptr, _f64, _vp],
-    "gc_bin_soft_assign": [_vp, _i32, _i64, _i32, _vp, _vp, _f64, _vp, _vp, _vp],
-    "gc_scan_bin_moment_match": [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _dptr, _f64, _f64, _vp, _vp],
-    "gc_scan_bins_fused": [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _f64, _dptr,
-                           _f64, _f64, _vp, _vp, _i32],
-    "gc_bins_task_plan": [_i32, _i64, _i32, _vp],
-    "gc_kappa_from_resultant_batch": [_vp, _i64, _vp, _f64, _f64, _f64, _f64, _vp],
-    "gc_domain_projection_psd_batch": [_vp, _i32, _i32, _vp, _f64, _vp, _vp],
-    "gc_pipeline_create": [_vp, _vp, _vp, C.POINTER(_vp)],
-    "gc_pipeline_destroy": [_vp],
-    "gc_pipeline_set_bins": [_vp, _vp],
-    "gc_pipeline_set_beliefs": [_vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_pipeline_get_beliefs": [_vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_pipeline_set_weights": [_vp, _vp],
-    "gc_pipeline_set_io_evidence": [_vp, _vp, _vp, _vp],
-    "gc_pipeline_set_io_mode": [_vp, _i32],
-    "gc_pipeline_stage_odom": [_vp, _i32, _vp, _vp, _vp, _vp],
-    "gc_pipeline_get_io_parts": [_vp, _vp],
-    "gc_pipeline_get_io_evidence": [_vp, _vp, _vp, _vp],
-    "gc_io_factor_batch": [_vp, _i32, _i32, _vp, _vp],
-    "gc_imu_vmf_gravity_tr_batch": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _dptr, _f64, _f64, _f64, _vp],
-    "gc_pipeline_set_iw": [_vp, _vp, _vp, _vp, _vp],
-    "gc_pipeline_get_iw": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_pipeline_set_map": [_vp, _vp],
-    "gc_pipeline_get_map": [_vp, _vp, _vp, _vp],
-    "gc_pipeline_stage_scan": [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
-    "gc_pointcloud2_parse": [_vp, _vp, _i64, _i32, _vp, _f64, _dptr, _dptr, _vp, _vp, _vp, _vp, _vp],
-    "gc_pipeline_stage_pointcloud2": [_vp, _i32, _vp, _i64, _i32, _vp, _f64, _dptr, _dptr, _vp, _vp, _vp],
-    "gc_pipeline_run_scan": [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _i64],
-    "gc_pipeline_scan_local": [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _i64],
-    "gc_pipeline_partial_len": [_vp],
-    "gc_pipeline_get_partial": [_vp, _vp],
-    "gc_pipeline_scan_finish": [_vp, _vp],
-    "gc_pipeline_set_lidar_mode": [_vp, _i32],
-    "gc_pipeline_scan_front": [_vp, _i32, _f64, _f64, _f64, _f64, _f64, _i64],
-    "gc_pipeline_front_poses": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
-    "gc_pipeline_get_front_poses": [_vp, _vp, _vp],
-    "gc_pipeline_get_front_twists": [_vp, _vp, _vp],
-    "gc_pipeline_get_front_hyp0": [_vp, _vp],
-    "gc_pipeline_set_lidar_evidence": [_vp, _vp, _vp, _vp, _i32],
-    "gc_pipeline_get_lidar_evidence": [_vp, _vp, _vp, _vp],
-    "gc_pipeline_scan_back": [_vp],
-    "gc_pipeline_get_combined": [_vp, _vp],
-    "gc_pipeline_get_hyp_diag": [_vp, _vp],
-    "gc_pipeline_get_hyp_conditioning": [_vp, _vp],
-    "gc_pipeline_get_projection_certs": [_vp, _vp, _vp],
-    "gc_pipeline_get_lpose6": [_vp, _vp],
-    "gc_pipeline_get_bin_stats": [_vp, _vp, _vp, _vp],
-    "gc_pipeline_get_hyp_stats": [_vp, _vp, _vp, _vp],
-    "gc_pipeline_attach_comm": [_vp, _vp],
-    "gc_pipeline_comm_size": [_vp],
-    "gc_pipeline_attach_primitive_map": [_vp, _vp, _f64],
-    "gc_pipeline_get_scan_map_pose": [_vp, _vp],
-    "gc_pipeline_map_colors_stale": [_vp],
-    "gc_pipeline_get_scan_map_count": [_vp, C.POINTER(C.c_int64)],
-    "gc_pipeline_set_scan_map_mode": [_vp, _i32],
-    "gc_pipeline_set_exchange_timing": [_vp, _i32],
-    "gc_pipeline_exchange_ms": [_vp, C.POINTER(C.c_float)],
-    "gc_pipeline_set_stage_timing": [_vp, _i32],
-    "gc_pipeline_stage_ms": [_vp, _vp],
-    "gc_pipeline_host_stats": [_vp, _vp, _i32],
-    "gc_pipeline_set_inscan_certs": [_vp, _i32],
-    "gc_pipeline_set_predict_route": [_vp, _i32],
-    "gc_pipeline_set_bin_scatter_all": [_vp, _i32],
-    "gc_comm_unique_id": [_vp],
-    "gc_comm_init": [_vp, _i32, _i32, _vp, C.POINTER(_vp)],
-    "gc_comm_destroy": [_vp],
-    "gc_comm_abort": [_vp],
-    "gc_comm_healthy": [_vp, C.POINTER(C.c_int32)],
-    "gc_comm_allgather_f64": [_vp, _vp, _vp, _vp, _i64],
-    "gc_lie_batch": [_vp, _i32, _i64, _vp, _vp],
-    "gc_belief_world_pose_batch": [_vp, _i32, _vp, _vp, _vp, _f64, _vp, _vp],
-    "gc_spd_inverse_lifted_batch": [_vp, _i32, _i32, _vp, _f64, _vp],
-    "gc_predict_diffusion_batch": [_vp, _i32, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp],
-    "gc_smooth_window_weights": [_vp, _i32, _vp, _f64, _f64, _f64, _vp],
-    "gc_preintegrate_imu_batch": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _dptr, _vp],
-    "gc_imu_meas_iw_suffstats_batch": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _vp],
-    "gc_matrix_fisher_batch": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp],
-    "gc_planar_translation_batch": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64,
-                                    _vp],
-    "gc_excitation_scaling_batch": [_vp, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _vp],
-    "gc_fusion_scale_batch": [_vp, _i32, _vp, _f64, _f64, _f64, _f64, _vp],
-    "gc_info_fusion_additive_batch": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp],
-    "gc_recompose_batch": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp],
-    "gc_anchor_drift_batch": [_vp, _i32, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp],
-    "gc_iw_process_suffstats_batch": [_vp, _i32, _vp, _vp, _vp, _vp, _f64, _vp, _vp],
-    "gc_iw_process_apply": [_vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp],
-    "gc_iw_process_Q": [_vp, _vp, _vp, _f64, _vp],
-    "gc_iw_meas_apply": [_vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp],
-    "gc_hypothesis_barycenter": [_vp, _i32, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp],
-    "gc_primitive_map_fuse": [_vp, _vp, _vp, _vp, _f64, _f64, _f64, _i64, _vp],
-    "gc_primitive_map_record_layout": [_i32, _vp, _vp],
-    "gc_copy_strided": [_vp, _vp, _i64, _vp, _i64, _i64, _i64],
-    "gc_primitive_map_forget": [_vp, _vp, _i64, _i64, _f64],
-    "gc_primitive_map_recency_inflate": [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp],
-    "gc_primitive_map_cull": [_vp, _vp, _i64, _i64, _f64, _i64, _vp],
-    "gc_primitive_map_insert_masked": [_vp, _vp, _i64, _i64, _vp, _f64, _i64, _f64, _i64, _vp, _vp, _vp],
-    "gc_primitive_map_merge_reduce": [_vp, _vp, _i64, _i64, _f64, _i32, _f64, _f64, _vp],
-    "gc_primitive_map_update": [_vp, _vp, _vp, _vp, _vp, _f64, _i64, _i64, _vp],
-    "gc_primitive_map_maintain": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp],
-    "gc_primitive_map_recency_inflate_tiles": [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _f64, _f64, _vp],
-    "gc_primitive_map_tile_export": [_vp, _vp, _i64, _i64, _vp],
-    "gc_primitive_map_tile_import": [_vp, _vp, _i64, _i64, _vp],
-    "gc_primitive_map_tile_reset": [_vp, _vp, _i64, _i64],
-    "gc_association_candidate_stats": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f64, _vp],
-    "gc_extract_map_view": [_vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp],
-    "gc_associate_primitives_ot": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                   _vp, _vp],
-    "gc_visual_pose_evidence": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _f64,
-                                _vp, _vp, _vp, _vp],
-    "gc_extract_lidar_surfels": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                 C.POINTER(C.c_int32)],
-    "gc_lidar_depth_evidence": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_camera_measurement_batch": [_vp, _i64, _vp, _vp, _vp, _i64] + [_vp] * 11 + [_vp, _vp, _f64, _f64, _i32, _i32,
-                                                                                    _i32, _f64] + [_vp] * 14,
-    "gc_measurement_batch_from_camera_splats": [_vp, _i64] + [_vp] * 7 + [_i32, _i32, _i32, _f64] + [_vp] * 9,
-    "gc_camera_features_lift": [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp] + [_vp] * 12,
-    "gc_keypoints_plan": [_i32, _i32, _vp, _vp, _vp, _vp],
-    "gc_keypoints_resize_table": [_i64, _i64, _vp, _vp],
-    "gc_keypoints_detect": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gc_renderable_batch_from_view": [_vp, _vp, _f64, _vp, C.POINTER(C.c_int64)],
-    "gc_bev_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
-    "gc_render_ewa_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp],
-    "gc_splat_indices_for_tile": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _vp, C.POINTER(C.c_int32)],
-    "gc_render_tile_ewa": [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _f64, _vp],
-    "gc_fbm_at_positions": [_vp, _i64, _vp, _i32, _f64, _i64, _vp],
-    "gc_camera_splat_prep": [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
-    "gc_render_depth_tiles": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp] + [_vp] * 7,
-}
-
-GC_PCFG_LEN = 22
-GC_PIPE_MAX_SLOTS = 8
-GC_MAP_REC = 26
-GC_MAP_DER = 17
-GC_IO_CERT = 10
-GC_IO_PARTS = 40
-GC_IO_GIVEN, GC_IO_COMPUTED = 0, 1
-GC_LIDAR_BINS, GC_LIDAR_GIVEN = 0, 1
-GC_LIDAR_CERT = 6
-GC_IOF_IN = 64
-GC_IOF_OUT = 484 + 22 + 16
-(GC_IOF_ODOM_QUADRATIC, GC_IOF_IMU_GYRO_ROTATION, GC_IOF_IMU_PREINT_FACTOR, GC_IOF_PLANAR_Z_PRIOR,
- GC_IOF_VELOCITY_Z_PRIOR, GC_IOF_ODOM_VELOCITY, GC_IOF_ODOM_YAWRATE, GC_IOF_KINEMATIC, GC_IOF_IMU_DEPENDENCE,
- GC_IOF_ODOM_DEPENDENCE) = range(10)
-GC_HYP_DIAG = 40
-GC_STAGE_N = 8
+# what the header cannot say: the names of the GC_STAGE_N stage times and of the GC_HS_* host statistics
 GC_STAGE_NAMES = ("predict", "bins", "evidence", "combine_local", "exchange", "combine_final", "map_update", "total")
-GC_HOST_STATS = 16
 GC_HS_NAMES = ("scans", "scan_enqueue_ms", "scan_enqueue_max_ms", "scan_wait_ms", "scan_wait_max_ms", "stages",
                "stage_work_ms", "stage_work_max_ms", "stage_wait_ms", "stage_wait_max_ms", "host_syncs", "h2d_bytes",
                "d2h_bytes", "jit_recompiles")
-GC_COMB_LEN = 484 + 22 + 22 + 6 + 16
-# gc_pipeline_get_projection_certs layout (include/gcslam.h GC_PCERT_*)
-GC_PCERT_SCAN = 12
-GC_PCERT_BARY, GC_PCERT_PROC0, GC_PCERT_MEAS0, GC_PCERT_Q = 0, 1, 8, 11
-GC_COMM_ID_BYTES = 128
-GC_PRED_CERT = 8
-GC_PREINT_OUT = 32
-GC_MF_OUT = 66
-GC_PT_OUT = 26
-GC_RECOMPOSE_OUT = 19
-GC_DRIFT_OUT = 3
-GC_FUSION_ROW = 8
-GC_FUSION_OUT = 4
-GC_BARY_CERT = 16
-GC_VPE_PARTS = 26
-GC_VPE_CERT = 4
-GC_SURFEL_CFG_LEN = 17
-GC_SURFEL_MAX_CELLS = 16384     # gc_surfel.hip: cell keys are below 2^14
-GC_SURFEL_MAX_OCCUPANTS = 1024  # gc_surfel.hip: bucket slots per cell
-GC_CAM_CFG_LEN = 23
-GC_CAM_EV = 9
-GC_CAM_MAX_NEAR = 1024          # gc_camsplat.hip: in-radius LiDAR points one query can hold
-GC_CAM_MAX_POINTS = 1 << 22
-GC_CAM_MAX_QUERIES = 4096
-GC_CAM_MAX_FIT_POINTS = 256     # gc_camsplat.hip: one fitted point per thread
-GC_CAMFEAT_CFG_LEN = 24
-GC_CAMFEAT_AUX = 6
-GC_KP_CFG_LEN = 6
-GC_KP_MAX_LEVELS = 16
-GC_KP_PLAN_ROW = 5
-GC_KP_COUNTS_LEN = 49
-
-
-class PipelineDims(C.Structure):
-    _fields_ = [("H_total", C.c_int32), ("h_begin", C.c_int32), ("h_count", C.c_int32), ("B", C.c_int32),
-                ("M", C.c_int32), ("world_size", C.c_int32), ("rank", C.c_int32), ("geom_hyps", C.c_int32),
-                ("n_in_max", C.c_int64), ("n_cap", C.c_int64)]
 
 _lib = None
 _lock = threading.Lock()
@@ -254,12 +54,9 @@ def lib():
                     raise RuntimeError(f"libgcslam.so not found at {LIB_PATH}: build it with "
                                        "`make -C fl-slam_amd` (there is no CPU fallback)")
                 L = C.CDLL(LIB_PATH)
-                for name, argt in SIGNATURES.items():
+                for name, (argtypes, restype) in PROTOTYPES.items():
                     fn = getattr(L, name)
-                    fn.argtypes = argt
-                    fn.restype = C.c_int32
-                L.gc_last_error.argtypes = [_vp]
-                L.gc_last_error.restype = C.c_char_p
+                    fn.argtypes, fn.restype = argtypes, restype
                 _lib = L
     return _lib
 

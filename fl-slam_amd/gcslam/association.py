@@ -76,11 +76,7 @@ class AssociationConfig:
     recency_decay_lambda: float = GC_RECENCY_DECAY_LAMBDA
 
 
-class _ViewStruct(C.Structure):
-    _fields_ = [("n_tiles", C.c_int32), ("m_tile_view", C.c_int32), ("n_lobes", C.c_int32), ("pad_", C.c_int32)] + \
-               [(k, C.c_void_p) for k in (
-                   "tile_ids", "candidate_tile_ids", "candidate_slots", "valid_mask", "positions", "covariances",
-                   "directions", "kappas", "weights", "primitive_ids", "last_supported_scan_seq", "etas", "colors")]
+_ViewStruct = _abi.STRUCTS["gc_map_view"]  # four int32, then tile_ids and the view's arrays
 
 
 class DeviceMapView:

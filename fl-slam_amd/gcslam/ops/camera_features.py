@@ -25,8 +25,8 @@ from .keypoint_detector import DeviceKeypoints
 DEPTH_SAMPLE_MODES = ("nearest", "median3", "median5", "hex")  # the codes 0..3 of the GC_CAMFEAT_CFG_LEN vector
 DEPTH_MODELS = ("linear", "quadratic")                         # the codes 0, 1
 AUX_NAMES = ("depth_sigma_c_sq", "z_m", "n_window", "n_fit", "lam_min", "K")  # the columns of aux
-MAX_RADIUS = 3          # gc_camfeat.hip: one lane per window pixel, (2 r + 1)^2 <= 64
-MAX_PIXELS = 1 << 26
+MAX_RADIUS = _abi.GC_CAMFEAT_MAX_RADIUS  # gc_camfeat.hip: one lane per window pixel, (2 r + 1)^2 <= 64
+MAX_PIXELS = _abi.GC_IMAGE_MAX_PIXELS
 
 
 @dataclass(frozen=True)

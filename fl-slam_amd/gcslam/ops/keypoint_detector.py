@@ -22,7 +22,7 @@ import numpy as np
 
 from .. import _abi
 
-MAX_PIXELS = 1 << 26
+MAX_PIXELS = _abi.GC_IMAGE_MAX_PIXELS
 
 
 @dataclass(frozen=True)

@@ -19,6 +19,8 @@ from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tu
 import numpy as np
 
 from . import _abi
+from ._abi import (GC_MAP_MAINTAIN_STATS_TILE, GC_MAP_UPDATE_MAX_ACTIVE, GC_MAP_UPDATE_MAX_INSERT, GC_MAP_UPDATE_MAX_K,
+                   GC_MAP_UPDATE_MAX_ROWS, GC_MAP_UPDATE_STATS_HEAD, GC_MAP_UPDATE_STATS_TILE)
 from .certificates import CertBundle, ExpectedEffect, InfluenceCert, MapUpdateCert
 from .constants import (GC_ASSOC_BLOCK_SIZE, GC_CHART_ID, GC_EPS_LIFT, GC_EPS_MASS, GC_EPS_PSD, GC_H_TILE,
                         GC_K_INSERT_TILE, GC_K_MERGE_PAIRS_PER_TILE, GC_PRIMITIVE_CULL_WEIGHT_THRESHOLD,
@@ -33,20 +35,9 @@ _COL = ("cam_mass", "lidar_mass", "rgb_cam_accum", "rgb_cam_denom", "rgb", "colo
 _MAINT = ("valid_mask", "created_timestamps", "primitive_ids")
 
 
-class _MapStruct(C.Structure):
-    _fields_ = [("m_slots", C.c_int64), ("n_lobes", C.c_int32), ("colors_current", C.c_int32)] + \
-               [(k, C.c_void_p) for k in _F64 + _I64 + _COL + _MAINT] + [("slot_bytes", C.c_int64)]
-
-
-class _InsertStruct(C.Structure):
-    _fields_ = [("K", C.c_int64)] + [(k, C.c_void_p) for k in (
-        "Lambdas", "thetas", "etas", "weights", "valid_mask", "colors", "sources")]
-
-
-class _FuseStruct(C.Structure):
-    _fields_ = [("K", C.c_int64)] + [(k, C.c_void_p) for k in (
-        "target_slots", "Lambdas", "thetas", "etas", "weights", "responsibilities", "valid_mask", "colors",
-        "sources")]
+_MapStruct = _abi.STRUCTS["gc_primitive_map"]  # its pointers are _F64 + _I64 + _COL + _MAINT, in that order
+_InsertStruct = _abi.STRUCTS["gc_insert_batch"]
+_FuseStruct = _abi.STRUCTS["gc_fuse_batch"]
 
 
 class TileMove(NamedTuple):
@@ -721,11 +712,7 @@ def _merge_finish(atlas_map, tile_id: int, state: int, n_merged: int, count: int
 
 
 # ----------------------------------------------------------------------------- the post-pose map update
-GC_MAP_UPDATE_MAX_ROWS = 8192    # include/gcslam.h: the insert plan's LDS holds 13 B per measurement row
-GC_MAP_UPDATE_MAX_INSERT = 1024  # and 13 B per proposal
-GC_MAP_UPDATE_MAX_ACTIVE = 64
-GC_MAP_UPDATE_MAX_K = 64
-_MU_HEAD, _MU_TILE = 4, 8        # GC_MAP_UPDATE_STATS_HEAD / _TILE
+_MU_HEAD, _MU_TILE = GC_MAP_UPDATE_STATS_HEAD, GC_MAP_UPDATE_STATS_TILE
 
 _MU_BATCH = (("Lambdas", np.float64, 9), ("thetas", np.float64, 3), ("etas", np.float64, None),
              ("weights", np.float64, 1), ("valid_mask", np.uint8, 1), ("colors", np.float64, 3),
@@ -734,16 +721,8 @@ _MU_ASSOC = (("responsibilities", np.float64), ("candidate_tile_ids", np.int64),
              ("row_masses", np.float64))
 
 
-class _MapUpdateIn(C.Structure):
-    _fields_ = [("N", C.c_int64), ("m_tile", C.c_int64), ("K", C.c_int32), ("n_active", C.c_int32),
-                ("k_insert", C.c_int32), ("block_size", C.c_int32)] + \
-               [(k, C.c_void_p) for k, _, _ in _MU_BATCH] + [(k, C.c_void_p) for k, _ in _MU_ASSOC] + \
-               [("active_keys", C.c_void_p), ("active_dense", C.c_void_p), ("h_active_dense", C.c_void_p)]
-
-
-class _MapUpdateOut(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("insert_indices", "insert_valid", "insert_target_slots", "new_ids",
-                                          "prop_Lambdas", "prop_thetas", "prop_weights", "stats")]
+_MapUpdateIn = _abi.STRUCTS["gc_map_update_in"]  # its pointers: _MU_BATCH, _MU_ASSOC, then the active tiles
+_MapUpdateOut = _abi.STRUCTS["gc_map_update_out"]
 
 
 @dataclass
@@ -763,7 +742,7 @@ class MapUpdateConfig:
     max_tile_size: int = GC_PRIMITIVE_MERGE_MAX_TILE_SIZE
 
 
-_MM_TILE = 8  # GC_MAP_MAINTAIN_STATS_TILE
+_MM_TILE = GC_MAP_MAINTAIN_STATS_TILE
 
 
 @dataclass

@@ -30,16 +30,11 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _abi
+from ._abi import GC_BEV_CFG_LEN, GC_CAMVIEW_CFG_LEN, GC_RENDER_MAX_CAP, GC_RENDER_MAX_TILE, GC_RENDER_MAX_VIEWS
 from .association import DeviceMapView, extract_atlas_map_view
 from .constants import GC_EPS_LIFT
 from .ops.camera_splats import PinholeIntrinsics
 from .primitive_map import DevicePrimitiveMap
-
-GC_BEV_CFG_LEN = 11
-GC_CAMVIEW_CFG_LEN = 13
-GC_RENDER_MAX_VIEWS = 32   # gc_render.hip: the views travel as one kernel argument
-GC_RENDER_MAX_CAP = 256    # gc_render.hip: splat records one tile holds in LDS
-GC_RENDER_MAX_TILE = 32    # rendering.py:267
 
 
 # ---------------------------------------------------------------------------------------------
@@ -131,14 +126,8 @@ class RenderablePrimitiveBatch:
     last_supported_scan_seq: Optional[np.ndarray] = None
 
 
-class _BatchStruct(C.Structure):
-    _fields_ = [("n_lobes", C.c_int32), ("pad_", C.c_int32)] + \
-               [(k, C.c_void_p) for k in ("mu_world", "Sigma_world", "Lambda_world", "eta", "mass", "color",
-                                          "primitive_ids", "last_supported_scan_seq")]
-
-
-class _SplatStruct(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("means_px", "Sigmas_inv", "alphas", "colors", "fbm", "Sigmas_bev")]
+_BatchStruct = _abi.STRUCTS["gc_render_batch"]  # n_lobes, pad_, then the arrays of _BATCH_SHAPES
+_SplatStruct = _abi.STRUCTS["gc_bev_splats"]
 
 
 _BATCH_SHAPES = dict(mu_world=((3,), np.float64), Sigma_world=((3, 3), np.float64), Lambda_world=((3, 3), np.float64),
@@ -406,8 +395,7 @@ class CameraRender:
     device: Dict[str, _abi.DeviceArray]
 
 
-class _CamSplatStruct(C.Structure):
-    _fields_ = [(k, C.c_void_p) for k in ("means_px", "Sigmas_inv", "depths", "radii", "alphas", "colors", "valid")]
+_CamSplatStruct = _abi.STRUCTS["gc_cam_splats"]
 
 
 def camera_from_world(pose, R_base_camera=None, t_base_camera=None, *, ctx=None) -> np.ndarray:

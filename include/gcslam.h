@@ -861,11 +861,12 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
  * Bounds (the insert plan keeps one workgroup's scores, in-tile flags and proposals in LDS:
  * 13 B per measurement row and 13 B per proposal of the CU's 160 KiB):
  *   1 <= N <= GC_MAP_UPDATE_MAX_ROWS, 1 <= k_insert <= min(N, m_tile, GC_MAP_UPDATE_MAX_INSERT),
- *   1 <= n_active <= GC_MAP_UPDATE_MAX_ACTIVE, 1 <= K <= 64.
+ *   1 <= n_active <= GC_MAP_UPDATE_MAX_ACTIVE, 1 <= K <= GC_MAP_UPDATE_MAX_K.
  * ------------------------------------------------------------------------------------------ */
 #define GC_MAP_UPDATE_MAX_ROWS 8192
 #define GC_MAP_UPDATE_MAX_INSERT 1024
 #define GC_MAP_UPDATE_MAX_ACTIVE 64
+#define GC_MAP_UPDATE_MAX_K 64
 /* per-call statistics (device doubles): [0] fused_mass_total, [1] sum over blocks of the distinct
    in-range slot numbers of the block (n_fused = n_active x this), [2..3] unused, then per active
    tile a at GC_MAP_UPDATE_STATS_HEAD + GC_MAP_UPDATE_STATS_TILE * a: [0] valid count of the tile
@@ -1095,6 +1096,9 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
                                 double* h_cert);
 
 #define GC_SURFEL_CFG_LEN 17
+#define GC_SURFEL_MAX_POINTS (1 << 22)  /* N */
+#define GC_SURFEL_MAX_CELLS 16384       /* each grid size, and the cells in all: cell keys are below 2^14 */
+#define GC_SURFEL_MAX_OCCUPANTS 1024    /* hex3d_max_occupants: bucket slots per cell */
 /* extract_lidar_surfels (operators/lidar_surfel_extraction.py:219-431; MA-hex hash grid
    common/ma_hex_web.py:221-303; batch rows structures/measurement_batch.py:262-347): the LiDAR
    slice of a MeasurementBatch from the N deskewed points (N, 3), timestamps (N) and weights (N) of
@@ -1134,6 +1138,10 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
 #define GC_CAM_EV 9          /* per query: Lambda_A theta_A Lambda_B theta_B Lambda_ell theta_ell, then Route
                                 B's z*, sigma^2 and w (NaN, NaN, 0 where Route B does not run) */
 #define GC_CAM_MAX_NEAR 1024 /* in-radius LiDAR points one query can hold */
+#define GC_CAM_MAX_POINTS (1 << 22)  /* N */
+#define GC_CAM_MAX_QUERIES 4096      /* rows of one camera batch: the query pixels M here, the keypoints of
+                                        gc_camera_features_lift and nfeatures of gc_keypoints_detect */
+#define GC_CAM_MAX_FIT_POINTS 256    /* lidar_ray_plane_fit_max_points: one fitted point per thread */
 /* lidar_depth_evidence (frontend/sensors/lidar_camera_depth_fusion.py:389-442; _project_camera :80-96,
    Route A :99-164, Route B :242-386, _fit_plane_weighted :207-239): the LiDAR depth evidence of M
    query pixels d_uv (M, 2) from N points in the camera frame (N, 3). h_intrinsics (host) = [fx, fy,
@@ -1190,6 +1198,9 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
 #define GC_CAMFEAT_AUX 6      /* per keypoint: depth_sigma_c_sq (NaN without a valid depth), z_m (NaN
                                  without), the depth window's valid count, the quadratic fit's point
                                  count (0 without a valid depth), lam_min and K (0 without a fit) */
+#define GC_CAMFEAT_MAX_RADIUS 3       /* max(1, hex_radius), max(1, quad_fit_radius): one lane per window pixel */
+#define GC_IMAGE_MAX_PIXELS (1 << 26) /* H W of an image, here and in the keypoint detector (and each axis of
+                                         gc_keypoints_resize_table) */
 /* The image side of the camera features (src/visual_feature_node.cpp:493-652 without ORB, and what
    _feature_batch_to_list makes of the message, backend/backend_node.py:1589-1645): M keypoints d_kp
    (M, 3) = (u, v, response) in f64, the depth image d_depth (float32, H x W, row-major, metres before
@@ -1323,6 +1334,10 @@ typedef struct gc_bev_splats {
   double* Sigmas_bev; /* (n_views, n, 2, 2) P Sigma P^T itself; may be NULL */
 } gc_bev_splats;
 
+/* The renderers' limits, BEV and camera view alike. */
+#define GC_RENDER_MAX_VIEWS 32 /* n_views: the views travel by value as one kernel argument */
+#define GC_RENDER_MAX_CAP 256  /* cap: splat records one tile holds in LDS */
+#define GC_RENDER_MAX_TILE 32  /* tile_size (rendering.py:267, :320 clamp it to [1, 32]) */
 /* Rows [0, n) of a batch as 2D splats, per view v with h_P[v] (2, 3) and h_view_dirs[v] (3) (host):
    mu_bev = P mu, Sigma_bev = (P Sigma) P^T (pushforward_gaussian_3d_to_2d, bev_pushforward.py:59-64);
    means_px = (mu_bev - origin_xy) px_per_m; Sigmas_inv = the closed-form inverse of

@@ -1,11 +1,13 @@
 """C-ABI surface checks that need no GPU: the library loads and exports every entry point
-include/gcslam.h declares; the Python binding covers them; argument errors map to ValueError."""
+include/gcslam.h declares; the binding's header reader takes the subset of C the header uses and fails
+loudly, naming the line, on anything else; argument errors map to ValueError."""
 
 import os
-import re
 import ctypes
 
 import pytest
+
+from gcslam import _abi, _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gcslam.h")
@@ -13,13 +15,13 @@ LIB = os.path.join(ROOT, "fl-slam_amd", "gcslam", "libgcslam.so")
 
 
 def declared():
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:int32_t|const char\*)\s+(gc_[a-z0-9_]+)\s*\(", txt, re.M)))
+    assert os.path.samefile(_header.HEADER_PATH, HEADER)
+    return sorted(_header.load(HEADER)[0])
 
 
 def test_header_declares_entries():
     names = declared()
-    assert "gc_ctx_create" in names and "gc_scan_bins_fused" in names
+    assert "gc_ctx_create" in names and "gc_scan_bins_fused" in names and "gc_iw_process_Q" in names
     assert len(names) >= 20
 
 
@@ -30,15 +32,95 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
-def test_python_binding_covers_header():
-    from gcslam import _abi
-    names = set(declared()) - {"gc_last_error"}
-    assert names <= set(_abi.SIGNATURES), sorted(names - set(_abi.SIGNATURES))
+SNIPPET = """
+/* a header in the manner of gcslam.h */
+#define GC_OK 0
+#define GC_ROW (484 + 22 + 16)   /* L, h, extras (16) */
+#define GC_KEYS (1 << 23)
+#define GC_TWO_ROWS (2 * GC_ROW - GC_OK)
+#define GC_TAU_MIN 3e-3
+#define GC_AT(B) ((B) + 1)
+typedef struct gc_ctx gc_ctx;
+struct gc_map; /* defined below */
+typedef struct gc_map {
+  int64_t m_slots;       /* (M), a comment; with a semicolon */
+  int32_t n_lobes;
+  const double* const weights;
+  uint8_t** planes;
+} gc_map;
+typedef struct {
+  float scale;
+  uint64_t bytes;
+} gc_dims;
+int32_t gc_version(void);
+const char* gc_last_error(const gc_ctx* ctx);
+int32_t gc_update_Q(gc_ctx* ctx, const struct gc_map* map, /* the map (device), as gc_fuse(a, b) takes it */
+                    const double* const d_in, void** d_out,
+                    int64_t n, double eps,   // one, two
+                    float gain, uint64_t bytes, const gc_dims* dims);
+"""
+
+
+def test_reader_takes_the_headers_subset():
+    protos, structs, consts = _header.parse(SNIPPET)
+    vp = ctypes.c_void_p
+    assert protos == {
+        "gc_version": ([], ctypes.c_int32),
+        "gc_last_error": ([vp], ctypes.c_char_p),
+        "gc_update_Q": ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_float, ctypes.c_uint64, vp],
+                        ctypes.c_int32)}
+    assert consts == {"GC_OK": 0, "GC_ROW": 522, "GC_KEYS": 8388608, "GC_TWO_ROWS": 1044, "GC_TAU_MIN": 3e-3}
+    assert "GC_AT" not in consts  # a function-like macro is skipped by rule
+    assert type(consts["GC_KEYS"]) is int and type(consts["GC_TAU_MIN"]) is float
+    assert sorted(structs) == ["gc_dims", "gc_map"]
+    assert structs["gc_map"]._fields_ == [("m_slots", ctypes.c_int64), ("n_lobes", ctypes.c_int32), ("weights", vp),
+                                          ("planes", vp)]
+    assert structs["gc_dims"]._fields_ == [("scale", ctypes.c_float), ("bytes", ctypes.c_uint64)]
+    assert issubclass(structs["gc_map"], ctypes.Structure) and ctypes.sizeof(structs["gc_map"]) == 8 + 4 + 4 + 8 + 8
+
+
+@pytest.mark.parametrize("bad, line, word", [
+    ("int32_t gc_f(gc_ctx* ctx,\n             size_t n);", 3, "size_t n"),                      # an unknown type token
+    ("int32_t gc_f(unsigned int n);", 2, "unsigned int n"),
+    ("typedef struct {\n  int64_t n;\n  double origin[3];\n} gc_s;", 4, "origin[3]"),        # an array member
+    ("typedef struct {\n  gc_ctx ctx;\n} gc_s;", 3, "gc_ctx ctx"),                            # a struct by value
+    ("typedef struct { int32_t n; } gc_s;\nint32_t gc_f(gc_s s);", 3, "gc_s s"),               # ... as an argument
+    ("#define GC_A 1\n#define GC_B (GC_A / 2)", 3, "GC_B"),                                    # an operator outside the set
+    ("#define GC_B (GC_LATER + 1)\n#define GC_LATER 1", 2, "GC_B"),                            # a name not defined yet
+    ("#define GC_N sizeof(int)", 2, "GC_N"),
+    ("#define GC_EMPTY", 2, "GC_EMPTY"),
+    ("int32_t gc_ok(void);\nvoid gc_f(int32_t n);", 3, "gc_f"),                                # a return type it does not bind
+    ("int32_t gc_f(int32_t (*cb)(int32_t));", 2, "gc_f"),                                      # a function pointer
+])
+def test_reader_fails_loudly(bad, line, word):
+    text = "typedef struct gc_ctx gc_ctx;\n" + bad + "\n"
+    with pytest.raises(RuntimeError) as e:
+        _header.parse(text, "snippet.h")
+    assert f"snippet.h:{line}:" in str(e.value) and word in str(e.value)
+    assert text.split("\n")[line - 1].strip() in str(e.value)  # the offending line itself
+
+
+def test_missing_header_is_a_runtime_error(tmp_path):
+    with pytest.raises(RuntimeError, match="gcslam.h not found"):
+        _header.load(str(tmp_path / "gcslam.h"))
+
+
+def test_binding_is_the_headers():
+    """What the package binds is what the reader yields from include/gcslam.h: every prototype with its
+    restype, the constants as _abi.GC_*, the structs under the names the operators use."""
+    protos, structs, consts = _header.load(HEADER)
+    assert _abi.SIGNATURES == {n: a for n, (a, _) in protos.items()}
+    assert _abi.PROTOTYPES["gc_last_error"] == ([ctypes.c_void_p], ctypes.c_char_p)
+    assert all(r is ctypes.c_int32 for n, (_, r) in _abi.PROTOTYPES.items() if n != "gc_last_error")
+    assert all(getattr(_abi, k) == v for k, v in consts.items()) and consts["GC_COMB_LEN"] == 550
+    assert "GC_PCERT_MF" not in consts and not hasattr(_abi, "GC_PCERT_MF")
+    assert len(_abi.GC_STAGE_NAMES) == _abi.GC_STAGE_N and len(_abi.GC_HS_NAMES) <= _abi.GC_HOST_STATS
+    assert _abi.PipelineDims._fields_ == structs["gc_pipeline_dims"]._fields_
+    assert len(structs) == 10
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libgcslam.so not built")
 def test_version_and_null_ctx_errors():
-    from gcslam import _abi
     assert _abi.lib().gc_version() >= 10000
     with pytest.raises(ValueError):
         _abi.check(_abi.lib().gc_ctx_synchronize(None))
@@ -50,7 +132,6 @@ def test_packed_map_record_layout():
     two 128-B lines of a 128-B-multiple record, no two fields overlapping, any lobe count; the Python
     map struct matches the header's field order and size."""
     import numpy as np
-    from gcslam import _abi
     from gcslam.primitive_map import _MapStruct
     widths = lambda L: [72, 24, 24 * L, 8, 8, 8, 8, 8, 8, 24, 8, 24, 24, 1, 8, 8]  # struct field order
     for L in range(1, 9):
