@@ -466,33 +466,23 @@ int32_t gc_extract_map_view(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_
 
 int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, const double* d_Lambdas,
                                    const double* d_thetas, const double* d_etas, const double* d_weights,
-                                   const uint8_t* d_valid, const gc_map_view* view, const double* h_cfg,
+                                   const uint8_t* d_valid, const gc_map_view* view, const gc_ot_cfg* cfg,
                                    double* d_resp_out, int32_t* d_cand_out, int64_t* d_cand_tile_out,
                                    int64_t* d_cand_slot_out, double* d_row_mass_out, double* d_cost_out,
                                    double* h_cert_out) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, view && h_cfg && h_cert_out, "NULL argument");
+  GC_CHECK_ARG(ctx, view && cfg && h_cert_out, "NULL argument");
   GC_CHECK_ARG(ctx, N >= 1 && n_lobes >= 1 && n_lobes <= kMapMaxLobes, "bad N or n_lobes");
   GC_CHECK_ARG(ctx, d_Lambdas && d_thetas && d_etas && d_valid && d_resp_out && d_cand_out && d_cand_tile_out &&
                         d_cand_slot_out && d_row_mass_out && d_cost_out,
                "NULL buffer");
   OTCfg c{};
-  c.K = (int)h_cfg[0];
-  c.iters = (int)h_cfg[1];
-  c.beta = h_cfg[2];
-  c.eps = h_cfg[3];
-  c.tau_a = h_cfg[4];
-  c.tau_b = h_cfg[5];
-  c.row_min = h_cfg[6] != 0.0;
-  c.wprop = h_cfg[7] != 0.0;
-  c.eps_mass = h_cfg[8];
-  c.h_tile = h_cfg[9];
-  c.r_xy = (int)h_cfg[10];
-  c.r_z = (int)h_cfg[11];
-  c.seq = (int64_t)h_cfg[12];
-  c.lam = h_cfg[13];
-  c.eps_lift = h_cfg[14];
+  c.K = (int)cfg->k_assoc; c.iters = (int)cfg->k_sinkhorn; c.beta = cfg->beta; c.eps = cfg->epsilon;
+  c.tau_a = cfg->tau_a; c.tau_b = cfg->tau_b; c.row_min = cfg->cost_subtract_row_min != 0.0;
+  c.wprop = cfg->weight_proportional != 0.0; c.eps_mass = cfg->eps_mass; c.h_tile = cfg->h_tile;
+  c.r_xy = (int)cfg->r_stencil_tiles_xy; c.r_z = (int)cfg->r_stencil_tiles_z; c.seq = (int64_t)cfg->scan_seq;
+  c.lam = cfg->recency_decay_lambda; c.eps_lift = cfg->eps_lift;
   GC_CHECK_ARG(ctx, c.K >= 1 && c.K <= kMaxK, "k_assoc must be in [1, 16]");
   GC_CHECK_ARG(ctx, c.iters >= 0 && c.r_xy >= 0 && c.r_z >= 0, "bad Sinkhorn / stencil config");
   const int n_xy = 3 * c.r_xy * (c.r_xy + 1) + 1;

@@ -329,32 +329,30 @@ __global__ void __launch_bounds__(kCfWave) k_cf_lift(CfArgs a) {
   x6[5] = K;
 }
 
-int cf_parse(gc_ctx* ctx, const double* k, const double* h, CfArgs* a) {
+int cf_parse(gc_ctx* ctx, const double* k, const gc_camfeat_cfg* h, CfArgs* a) {
   for (int q = 0; q < 4; ++q) GC_CHECK_ARG(ctx, fabs(k[q]) <= 1e300, "the intrinsics must be finite");
   GC_CHECK_ARG(ctx, k[0] != 0.0 && k[1] != 0.0, "fx and fy must not be 0");
-  for (int q = 0; q < GC_CAMFEAT_CFG_LEN; ++q) GC_CHECK_ARG(ctx, h[q] == h[q], "NaN in the configuration");
-  GC_CHECK_ARG(ctx, h[0] == 0.0 || h[0] == 1.0 || h[0] == 2.0 || h[0] == 3.0,
+  GC_CHECK_ARG(ctx, cfg_all<24>(h, [](double v) { return v == v; }), "NaN in the configuration");
+  const double mode = h->depth_sample_mode, rh = h->hex_radius, rq = h->quad_fit_radius, mp = h->quad_fit_min_points;
+  GC_CHECK_ARG(ctx, mode == 0.0 || mode == 1.0 || mode == 2.0 || mode == 3.0,
                "depth_sample_mode must be 0 (nearest), 1 (median3), 2 (median5) or 3 (hex)");
-  GC_CHECK_ARG(ctx, h[2] == 0.0 || h[2] == 1.0, "depth_model must be 0 (linear) or 1 (quadratic)");
+  GC_CHECK_ARG(ctx, h->depth_model == 0.0 || h->depth_model == 1.0, "depth_model must be 0 (linear) or 1 (quadratic)");
   // std::max(1, r) first (:303, :407)
-  GC_CHECK_ARG(ctx, h[12] == floor(h[12]) && h[12] <= (double)kCfMaxRadius && h[12] >= -2147483648.0,
+  GC_CHECK_ARG(ctx, rh == floor(rh) && rh <= (double)kCfMaxRadius && rh >= -2147483648.0,
                "hex_radius must be an integer with max(1, hex_radius) in [1, 3]");
-  GC_CHECK_ARG(ctx, h[13] == floor(h[13]) && h[13] <= (double)kCfMaxRadius && h[13] >= -2147483648.0,
+  GC_CHECK_ARG(ctx, rq == floor(rq) && rq <= (double)kCfMaxRadius && rq >= -2147483648.0,
                "quad_fit_radius must be an integer with max(1, quad_fit_radius) in [1, 3]");
-  GC_CHECK_ARG(ctx, h[14] == floor(h[14]) && h[14] >= 1.0 && h[14] <= 16777216.0,
-               "quad_fit_min_points must be an integer >= 1");
+  GC_CHECK_ARG(ctx, mp == floor(mp) && mp >= 1.0 && mp <= 16777216.0, "quad_fit_min_points must be an integer >= 1");
   a->fx = k[0]; a->fy = k[1]; a->cx = k[2]; a->cy = k[3];
-  a->mode = (int)h[0];
-  a->pixel_var = h[1] * h[1];  // :580
-  a->model = (int)h[2];
-  a->sigma0 = h[3]; a->sigma_slope = h[4]; a->min_depth = h[5]; a->max_depth = h[6]; a->validity_slope = h[7];
-  a->response_scale = h[8]; a->depth_scale = h[9]; /* h[10] cov_reg_eps: the node never reads it */
-  a->invalid_cov = h[11];
-  const int r_hex = h[12] < 1.0 ? 1 : (int)h[12];
-  a->rq = h[13] < 1.0 ? 1 : (int)h[13];
-  a->min_points = (int)h[14];
-  a->ridge = h[15]; a->nu = h[16]; a->w_min = h[17]; a->ma_tau = h[18]; a->ma_delta = h[19];
-  a->kappa0 = h[20]; a->kappa_alpha = h[21]; a->kappa_max = h[22]; a->kappa_min = h[23];
+  a->mode = (int)mode; a->pixel_var = h->pixel_sigma * h->pixel_sigma; /* :580 */ a->model = (int)h->depth_model;
+  a->sigma0 = h->depth_sigma0; a->sigma_slope = h->depth_sigma_slope; a->min_depth = h->min_depth_m;
+  a->max_depth = h->max_depth_m; a->validity_slope = h->depth_validity_slope;
+  a->response_scale = h->response_soft_scale; a->depth_scale = h->depth_scale;
+  a->invalid_cov = h->invalid_cov_inflate;  // cov_reg_eps before it: the node never reads it
+  const int r_hex = rh < 1.0 ? 1 : (int)rh; a->rq = rq < 1.0 ? 1 : (int)rq; a->min_points = (int)mp;
+  a->ridge = h->quad_fit_lstsq_eps; a->nu = h->student_t_nu; a->w_min = h->student_t_w_min; a->ma_tau = h->ma_tau;
+  a->ma_delta = h->ma_delta_inflate; a->kappa0 = h->kappa0; a->kappa_alpha = h->kappa_alpha;
+  a->kappa_max = h->kappa_max; a->kappa_min = h->kappa_min;
   // :304-312
   a->hx[0] = 0; a->hy[0] = 0;
   for (int q = 0; q < 6; ++q) {
@@ -373,13 +371,13 @@ using namespace gc;
 extern "C" {
 
 int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* d_depth, const uint8_t* d_rgb,
-                                int64_t M, const double* d_kp, const double* h_intrinsics, const double* h_cfg,
+                                int64_t M, const double* d_kp, const double* h_intrinsics, const gc_camfeat_cfg* cfg,
                                 double* d_uv, double* d_Lambda_c, double* d_theta_c, double* d_weight,
                                 double* d_kappa, double* d_mu_app, uint8_t* d_has_mu_app, double* d_color,
                                 uint8_t* d_has_color, double* d_xyz, double* d_cov_xyz, double* d_aux) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, h_intrinsics && h_cfg, "NULL argument");
+  GC_CHECK_ARG(ctx, h_intrinsics && cfg, "NULL argument");
   GC_CHECK_ARG(ctx, M >= 0 && M <= kCfMaxQueries, "M must be in [0, 4096]");
   GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && (int64_t)H * W <= kCfMaxPixels, "H and W must be >= 1 and H W <= 2^26");
   GC_CHECK_ARG(ctx, d_depth != nullptr, "NULL depth image");
@@ -387,7 +385,7 @@ int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* 
                                d_has_mu_app && d_color && d_has_color && d_xyz && d_cov_xyz && d_aux),
                "NULL keypoint or output buffer");
   CfArgs a = {};
-  if (int rc = cf_parse(ctx, h_intrinsics, h_cfg, &a)) return rc;
+  if (int rc = cf_parse(ctx, h_intrinsics, cfg, &a)) return rc;
   if (M == 0) return GC_OK;
   a.H = H; a.W = W; a.depth = d_depth; a.rgb = d_rgb; a.kp = d_kp;
   a.uv = d_uv; a.Lc = d_Lambda_c; a.thc = d_theta_c; a.weight = d_weight; a.kappa = d_kappa; a.mu = d_mu_app;

@@ -293,12 +293,13 @@ unsigned cam_blocks(int64_t threads) { return (unsigned)((threads + kRdT - 1) / 
 
 bool cam_finite(double x) { return fabs(x) <= 1e300; }
 
-// the configuration vector (GC_CAMVIEW_CFG_LEN doubles), checked
-int cam_cfg(gc_ctx* ctx, const double* h, CamCfg* c) {
-  for (int q = 0; q < GC_CAMVIEW_CFG_LEN; ++q) GC_CHECK_ARG(ctx, cam_finite(h[q]), "the configuration must be finite");
-  c->near = h[0]; c->far = h[1]; c->lowpass = h[2]; c->radius_sigma = h[3]; c->alpha_floor = h[4]; c->alpha_max = h[5];
-  c->alpha_skip = h[6]; c->t_stop = h[7]; c->bg[0] = h[8]; c->bg[1] = h[9]; c->bg[2] = h[10]; c->shade = h[11] != 0.0;
-  c->eps = h[12];
+// the configuration, checked
+int cam_cfg(gc_ctx* ctx, const gc_camview_cfg* h, CamCfg* c) {
+  GC_CHECK_ARG(ctx, cfg_all<13>(h, cam_finite), "the configuration must be finite");
+  c->near = h->near; c->far = h->far; c->lowpass = h->lowpass_px2; c->radius_sigma = h->radius_sigma;
+  c->alpha_floor = h->alpha_floor; c->alpha_max = h->alpha_max; c->alpha_skip = h->alpha_skip; c->t_stop = h->t_stop;
+  c->bg[0] = h->bg_r; c->bg[1] = h->bg_g; c->bg[2] = h->bg_b; c->shade = h->shade != 0.0;
+  c->eps = h->eps;
   GC_CHECK_ARG(ctx, c->near > 0.0 && c->far > c->near, "near must be > 0 and far > near");
   GC_CHECK_ARG(ctx, c->alpha_max > 0.0 && c->alpha_max <= 1.0, "alpha_max must be in (0, 1]");
   return GC_OK;
@@ -317,17 +318,17 @@ using namespace gc;
 extern "C" {
 
 int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_T_cw,
-                             const double* h_intrinsics, int32_t H, int32_t W, const double* h_cfg,
+                             const double* h_intrinsics, int32_t H, int32_t W, const gc_camview_cfg* cfg,
                              const gc_cam_splats* out) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, batch && h_T_cw && h_intrinsics && h_cfg && out, "NULL argument");
+  GC_CHECK_ARG(ctx, batch && h_T_cw && h_intrinsics && cfg && out, "NULL argument");
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
   GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
   if (int rc = cam_check_frame(ctx, H, W)) return rc;
   CamCfg c;
-  if (int rc = cam_cfg(ctx, h_cfg, &c)) return rc;
+  if (int rc = cam_cfg(ctx, cfg, &c)) return rc;
   double hv[kRdMaxViews * kCamView];
   for (int v = 0; v < n_views; ++v) {
     const double* T = h_T_cw + 16 * v;
@@ -372,9 +373,9 @@ int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t 
 }
 
 int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_cam_splats* splats, int32_t H, int32_t W,
-                              int32_t tile_size, int32_t cap, const double* h_cfg, double* d_images, double* d_alpha,
-                              double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts, int32_t* d_tile_survivors,
-                              int32_t* d_tile_indices) {
+                              int32_t tile_size, int32_t cap, const gc_camview_cfg* cfg, double* d_images,
+                              double* d_alpha, double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts,
+                              int32_t* d_tile_survivors, int32_t* d_tile_indices) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
   GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kRdMaxTile, "tile_size must be in [1, 32]");
@@ -383,9 +384,9 @@ int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_
   GC_CHECK_ARG(ctx, cap >= 1 && cap <= kRdMaxCap, "cap must be in [1, 256]");
   GC_CHECK_ARG(ctx, n >= 0, "n must be >= 0");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
-  GC_CHECK_ARG(ctx, h_cfg != nullptr, "NULL configuration");
+  GC_CHECK_ARG(ctx, cfg != nullptr, "NULL configuration");
   CamRasterArgs A;
-  if (int rc = cam_cfg(ctx, h_cfg, &A.c)) return rc;
+  if (int rc = cam_cfg(ctx, cfg, &A.c)) return rc;
   GC_CHECK_ARG(ctx, d_images && d_alpha && d_depth && d_n_contrib && d_tile_counts && d_tile_survivors && d_tile_indices,
                "NULL output buffer");
   TileGrid G;

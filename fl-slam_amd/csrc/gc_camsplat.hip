@@ -443,25 +443,29 @@ __global__ void __launch_bounds__(kCsT) k_cs_finish(CsFin a) {
   }
 }
 
-int cs_parse_cfg(gc_ctx* ctx, const double* h, CsCfg* c) {
-  for (int q = 0; q < GC_CAM_CFG_LEN; ++q) GC_CHECK_ARG(ctx, h[q] == h[q], "NaN in the configuration");
-  GC_CHECK_ARG(ctx, h[3] > 0.0 && h[3] <= 1e300, "lidar_projection_radius_pix must be > 0 and finite");
-  GC_CHECK_ARG(ctx, h[4] >= 1.0 && h[4] <= 16777216.0 && h[4] == floor(h[4]),
-               "lidar_plane_fit_min_points must be an integer >= 1");
-  GC_CHECK_ARG(ctx, h[12] >= 1.0 && h[12] <= (double)kCsMaxK && h[12] == floor(h[12]),
+int cs_parse_cfg(gc_ctx* ctx, const gc_cam_cfg* h, CsCfg* c) {
+  GC_CHECK_ARG(ctx, cfg_all<23>(h, [](double v) { return v == v; }), "NaN in the configuration");
+  GC_CHECK_ARG(ctx, h->lidar_projection_radius_pix > 0.0 && h->lidar_projection_radius_pix <= 1e300,
+               "lidar_projection_radius_pix must be > 0 and finite");
+  const double mp = h->lidar_plane_fit_min_points, k = h->lidar_ray_plane_fit_max_points;
+  GC_CHECK_ARG(ctx, mp >= 1.0 && mp <= 16777216.0 && mp == floor(mp), "lidar_plane_fit_min_points must be an integer >= 1");
+  GC_CHECK_ARG(ctx, k >= 1.0 && k <= (double)kCsMaxK && k == floor(k),
                "lidar_ray_plane_fit_max_points must be an integer in [1, 256]");
-  c->w_cam = h[0]; c->w_lidar = h[1]; c->gamma = h[2]; c->radius = h[3]; c->min_points = (int)h[4];
-  c->base_sigma = h[5]; /* h[6] lidar_incidence_sigma_scale: the reference never reads it */ c->var_min = h[7];
-  c->n0 = h[8]; c->alpha_cnt = h[9]; c->beta_mad = h[10]; c->gamma_repr = h[11]; c->max_points = (int)h[12];
-  c->delta = h[13]; c->alpha = h[14]; c->t_angle = h[15]; c->beta = h[16]; c->rho0 = h[17]; c->gamma_res = h[18];
-  c->eps = h[19]; c->z_min = h[20]; c->sigma_max_sq = h[21]; c->alpha_z = h[22];
+  c->w_cam = h->depth_fusion_weight_camera; c->w_lidar = h->depth_fusion_weight_lidar; c->gamma = h->gamma_lidar;
+  c->radius = h->lidar_projection_radius_pix; c->min_points = (int)mp; c->base_sigma = h->lidar_depth_base_sigma_m;
+  c->var_min = h->depth_var_min_m2; c->n0 = h->point_support_n0; c->alpha_cnt = h->point_support_alpha;
+  c->beta_mad = h->spread_mad_beta; c->gamma_repr = h->repr_gamma; c->max_points = (int)k;
+  c->delta = h->plane_intersection_delta; c->alpha = h->plane_angle_sigmoid_alpha;
+  c->t_angle = h->plane_angle_sigmoid_t; c->beta = h->plane_planarity_sigmoid_beta;
+  c->rho0 = h->plane_planarity_rho0; c->gamma_res = h->plane_residual_exp_gamma; c->eps = h->plane_fit_eps;
+  c->z_min = h->depth_min_m; c->sigma_max_sq = h->depth_sigma_max_sq; c->alpha_z = h->depth_min_sigmoid_alpha_z;
   return GC_OK;
 }
 
-int cs_parse_intr(gc_ctx* ctx, const double* h, CsIntr* K) {
-  for (int q = 0; q < 4; ++q) GC_CHECK_ARG(ctx, fabs(h[q]) <= 1e300, "the intrinsics must be finite");
-  GC_CHECK_ARG(ctx, h[0] != 0.0 && h[1] != 0.0, "fx and fy must not be 0");
-  K->fx = h[0]; K->fy = h[1]; K->cx = h[2]; K->cy = h[3];
+int cs_parse_intr(gc_ctx* ctx, const double* k4, CsIntr* K) {
+  for (int q = 0; q < 4; ++q) GC_CHECK_ARG(ctx, fabs(k4[q]) <= 1e300, "the intrinsics must be finite");
+  GC_CHECK_ARG(ctx, k4[0] != 0.0 && k4[1] != 0.0, "fx and fy must not be 0");
+  K->fx = k4[0]; K->fy = k4[1]; K->cx = k4[2]; K->cy = k4[3];
   return GC_OK;
 }
 
@@ -539,11 +543,11 @@ using namespace gc;
 extern "C" {
 
 int32_t gc_lidar_depth_evidence(gc_ctx* ctx, int64_t N, const double* d_points_cam, int64_t M, const double* d_uv,
-                                const double* h_intrinsics, const double* h_cfg, const double* d_point_weights,
+                                const double* h_intrinsics, const gc_cam_cfg* h, const double* d_point_weights,
                                 double* d_evidence, int32_t* d_counts) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, h_intrinsics && h_cfg, "NULL argument");
+  GC_CHECK_ARG(ctx, h_intrinsics && h, "NULL argument");
   GC_CHECK_ARG(ctx, N >= 0 && N <= kCsMaxPoints, "N must be in [0, 4194304]");
   GC_CHECK_ARG(ctx, M >= 0 && M <= kCsMaxQueries, "M must be in [0, 4096]");
   GC_CHECK_ARG(ctx, N == 0 || d_points_cam, "NULL point buffer");
@@ -551,7 +555,7 @@ int32_t gc_lidar_depth_evidence(gc_ctx* ctx, int64_t N, const double* d_points_c
   CsCfg cfg;
   CsIntr K;
   CsXf xf;
-  if (int rc = cs_parse_cfg(ctx, h_cfg, &cfg)) return rc;
+  if (int rc = cs_parse_cfg(ctx, h, &cfg)) return rc;
   if (int rc = cs_parse_intr(ctx, h_intrinsics, &K)) return rc;
   if (int rc = cs_parse_xf(ctx, nullptr, nullptr, &xf)) return rc;
   if (M == 0) return GC_OK;
@@ -567,7 +571,7 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                                     const double* d_theta_c, const double* d_weight, const double* d_kappa,
                                     const double* d_mu_app, const uint8_t* d_has_mu_app, const double* d_color,
                                     const uint8_t* d_has_color, const double* d_xyz, const double* d_cov_xyz,
-                                    const double* h_intrinsics, const double* h_cfg, double pixel_sigma,
+                                    const double* h_intrinsics, const gc_cam_cfg* h, double pixel_sigma,
                                     double timestamp_sec, int32_t n_feat, int32_t n_surfel, int32_t n_lobes,
                                     double eps_lift, double* d_Lambdas, double* d_thetas, double* d_etas,
                                     double* d_weights_out, int32_t* d_sources, int32_t* d_source_indices,
@@ -576,7 +580,7 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                                     double* d_evidence, int32_t* d_counts) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, h_intrinsics && h_cfg, "NULL argument");
+  GC_CHECK_ARG(ctx, h_intrinsics && h, "NULL argument");
   GC_CHECK_ARG(ctx, N >= 0 && N <= kCsMaxPoints, "N must be in [0, 4194304]");
   GC_CHECK_ARG(ctx, M >= 0 && M <= kCsMaxQueries, "M must be in [0, 4096]");
   GC_CHECK_ARG(ctx, N == 0 || d_points_base, "NULL point buffer");
@@ -591,7 +595,7 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                "NaN scalar argument");
   CsCfg cfg;
   CsFin a = {};
-  if (int rc = cs_parse_cfg(ctx, h_cfg, &cfg)) return rc;
+  if (int rc = cs_parse_cfg(ctx, h, &cfg)) return rc;
   if (int rc = cs_parse_intr(ctx, h_intrinsics, &a.K)) return rc;
   if (int rc = cs_parse_xf(ctx, h_R9, h_t3, &a.xf)) return rc;
   const int64_t n_total = (int64_t)n_feat + n_surfel;

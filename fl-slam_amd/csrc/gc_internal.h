@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -111,6 +112,13 @@ int carve_scratch(gc_ctx* ctx, Layout&& layout) {
   Carver c{(char*)scr};
   layout(c);
   return GC_OK;
+}
+
+// whether each of the n doubles of a configuration struct (a gc_*_cfg of gcslam.h: doubles only) passes ok
+template <int n, typename Cfg, typename Ok>
+bool cfg_all(const Cfg* c, Ok ok) {
+  static_assert(sizeof(Cfg) == n * sizeof(double), "a gc_*_cfg holds n doubles and nothing else");
+  return std::all_of(reinterpret_cast<const double*>(c), reinterpret_cast<const double*>(c) + n, ok);
 }
 
 // a run hash (gc_runs.h RunTable) of at least 2^kRunLoadShift x rows entries, every entry empty on return

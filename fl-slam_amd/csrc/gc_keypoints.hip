@@ -111,23 +111,20 @@ void kp_layout(Carver& c, const KpPlan& p, KpScratch* s) {
 bool kp_is_int(double v, double lo, double hi) { return v == floor(v) && v >= lo && v <= hi; }  // false for NaN
 
 // the checks of the configuration and the plan of step 2 (host arithmetic, contraction off)
-int kp_plan(gc_ctx* ctx, int64_t H, int64_t W, const double* h, KpPlan* p) {
+int kp_plan(gc_ctx* ctx, int64_t H, int64_t W, const gc_kp_cfg* h, KpPlan* p) {
   GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && H * W <= kKpMaxPixels, "H and W must be >= 1 and H W <= 2^26");
-  GC_CHECK_ARG(ctx, kp_is_int(h[0], 1.0, (double)kKpMaxFeatures), "nfeatures must be an integer in [1, 4096]");
-  GC_CHECK_ARG(ctx, fabs(h[1]) <= 3.40282347e38, "scale_factor must be finite as float32");  // false for NaN
-  const float sf = (float)h[1];
+  GC_CHECK_ARG(ctx, kp_is_int(h->nfeatures, 1.0, (double)kKpMaxFeatures), "nfeatures must be an integer in [1, 4096]");
+  GC_CHECK_ARG(ctx, fabs(h->scale_factor) <= 3.40282347e38, "scale_factor must be finite as float32");  // false for NaN
+  const float sf = (float)h->scale_factor;
   GC_CHECK_ARG(ctx, sf > 1.0f, "scale_factor must be > 1 as float32");
-  GC_CHECK_ARG(ctx, kp_is_int(h[2], 1.0, (double)kKpLevels), "nlevels must be an integer in [1, 16]");
-  GC_CHECK_ARG(ctx, kp_is_int(h[3], 4.0, 1024.0), "edge_threshold must be an integer in [4, 1024]");
-  GC_CHECK_ARG(ctx, kp_is_int(h[4], 1.0, 254.0), "fast_threshold must be an integer in [1, 254]");
-  GC_CHECK_ARG(ctx, fabs(h[5]) <= 1.79769313486231570815e308, "harris_k must be finite");
+  GC_CHECK_ARG(ctx, kp_is_int(h->nlevels, 1.0, (double)kKpLevels), "nlevels must be an integer in [1, 16]");
+  GC_CHECK_ARG(ctx, kp_is_int(h->edge_threshold, 4.0, 1024.0), "edge_threshold must be an integer in [4, 1024]");
+  GC_CHECK_ARG(ctx, kp_is_int(h->fast_threshold, 1.0, 254.0), "fast_threshold must be an integer in [1, 254]");
+  GC_CHECK_ARG(ctx, fabs(h->harris_k) <= 1.79769313486231570815e308, "harris_k must be finite");
   memset(p, 0, sizeof(*p));
   KpDev& d = p->d;
-  d.nfeatures = (int)h[0];
-  d.nlevels = (int)h[2];
-  d.edge = (int)h[3];
-  d.thr = (int)h[4];
-  p->harris_k = h[5];
+  d.nfeatures = (int)h->nfeatures; d.nlevels = (int)h->nlevels; d.edge = (int)h->edge_threshold;
+  d.thr = (int)h->fast_threshold; p->harris_k = h->harris_k;
   // quotas
   const double f = 1.0 / (double)sf;
   double nd = (double)d.nfeatures * (1.0 - f) / (1.0 - pow(f, (double)d.nlevels));
@@ -463,11 +460,11 @@ using namespace gc;
 
 extern "C" {
 
-int32_t gc_keypoints_plan(int32_t H, int32_t W, const double* h_cfg, int64_t* h_levels, double* h_scales,
+int32_t gc_keypoints_plan(int32_t H, int32_t W, const gc_kp_cfg* cfg, int64_t* h_levels, double* h_scales,
                           int64_t* h_bytes) {
-  GC_CHECK_ARG(nullptr, h_cfg && h_levels && h_scales && h_bytes, "NULL argument");
+  GC_CHECK_ARG(nullptr, cfg && h_levels && h_scales && h_bytes, "NULL argument");
   KpPlan p;
-  if (int rc = kp_plan(nullptr, H, W, h_cfg, &p)) return rc;
+  if (int rc = kp_plan(nullptr, H, W, cfg, &p)) return rc;
   for (int l = 0; l < kKpLevels; ++l) {
     int64_t* row = h_levels + GC_KP_PLAN_ROW * l;
     const bool on = l < p.d.nlevels;
@@ -495,14 +492,14 @@ int32_t gc_keypoints_resize_table(int64_t n_src, int64_t n_dst, int32_t* h_i0, i
 }
 
 int32_t gc_keypoints_detect(gc_ctx* ctx, int32_t H, int32_t W, int32_t channels, const uint8_t* d_image,
-                            const double* h_cfg, uint8_t* d_pyramid, double* d_kp, int32_t* d_meta,
+                            const gc_kp_cfg* cfg, uint8_t* d_pyramid, double* d_kp, int32_t* d_meta,
                             int32_t* d_counts) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, h_cfg != nullptr, "NULL configuration");
+  GC_CHECK_ARG(ctx, cfg != nullptr, "NULL configuration");
   GC_CHECK_ARG(ctx, channels == 1 || channels == 3, "channels must be 1 or 3");
   KpPlan p;
-  if (int rc = kp_plan(ctx, H, W, h_cfg, &p)) return rc;
+  if (int rc = kp_plan(ctx, H, W, cfg, &p)) return rc;
   GC_CHECK_ARG(ctx, d_image && d_pyramid && d_kp && d_meta && d_counts, "NULL image or output buffer");
   const KpDev& L = p.d;
   KpScratch s;

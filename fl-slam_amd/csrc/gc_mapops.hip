@@ -758,10 +758,10 @@ int32_t gc_primitive_map_insert_masked(gc_ctx* ctx, const gc_primitive_map* map,
   if (int rc = gc::insert_launch(ctx, map, slot0, n_slots, batch, timestamp, scan_seq, recency_decay_lambda,
                                  next_global_id, nullptr, d_target_slots_out, d_new_ids_out, scr, out))
     return rc;
-  double h[2];
-  if (int rc = download(ctx, h, out, sizeof(h))) return rc;
-  h_out2[0] = (int64_t)h[1];
-  h_out2[1] = (int64_t)h[0];
+  double counts[2];
+  if (int rc = download(ctx, counts, out, sizeof(counts))) return rc;
+  h_out2[0] = (int64_t)counts[1];
+  h_out2[1] = (int64_t)counts[0];
   return GC_OK;
 }
 
@@ -809,15 +809,16 @@ int32_t gc_primitive_map_merge_reduce(gc_ctx* ctx, const gc_primitive_map* map, 
 }
 
 int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, int32_t n_active,
-                                  const int32_t* d_active_dense, const int32_t* h_active_dense, const double* h_cfg,
-                                  int64_t max_primitives, int32_t max_pairs, int64_t max_tile_size,
-                                  int64_t max_sort_keys, double* d_stats) {
+                                  const int32_t* d_active_dense, const int32_t* h_active_dense,
+                                  const gc_map_maintain_cfg* cfg, int64_t max_primitives, int32_t max_pairs,
+                                  int64_t max_tile_size, int64_t max_sort_keys, double* d_stats) {
   if (int rc = check_tile(ctx, map, 0, 0, true)) return rc;  // joins the side stream first
   if (int rc = check_active_tiles(ctx, map, m_tile, n_active, d_active_dense, h_active_dense)) return rc;
   if (n_active == 0) return GC_OK;
-  GC_CHECK_ARG(ctx, h_cfg && d_stats, "NULL argument");
+  GC_CHECK_ARG(ctx, cfg && d_stats, "NULL argument");
   GC_CHECK_ARG(ctx, max_sort_keys >= 0, "max_sort_keys must be >= 0");
-  const double thr0 = h_cfg[0], gamma = h_cfg[1], merge_thr = h_cfg[2], eps_psd = h_cfg[3], eps_lift = h_cfg[4];
+  const double thr0 = cfg->primitive_cull_weight_threshold, gamma = cfg->primitive_forgetting_factor,
+               merge_thr = cfg->primitive_merge_threshold, eps_psd = cfg->eps_psd, eps_lift = cfg->eps_lift;
   const bool top = max_primitives >= 0;
   const int64_t slots = (int64_t)n_active * m_tile;
   GC_CHECK_ARG(ctx, !top || slots < ((int64_t)1 << 32), "max_primitives: the active tiles must hold < 2^32 slots");

@@ -310,11 +310,11 @@ using namespace gc;
 extern "C" {
 
 int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const gc_map_update_in* in,
-                                const double* h_pose6, const double* h_cfg, double timestamp, int64_t scan_seq,
-                                int64_t next_global_id, const gc_map_update_out* out) {
+                                const double* h_pose6, const gc_map_update_cfg* cfg, double timestamp,
+                                int64_t scan_seq, int64_t next_global_id, const gc_map_update_out* out) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, map && in && h_pose6 && h_cfg && out, "NULL argument");
+  GC_CHECK_ARG(ctx, map && in && h_pose6 && cfg && out, "NULL argument");
   if (int rc = gc::check_map(ctx, map, (int64_t)INT32_MAX, false)) return rc;
   GC_CHECK_ARG(ctx, map->valid_mask, "NULL map field");  // this entry's text for a missing valid_mask
   const int64_t N = in->N, K = in->K, m_tile = in->m_tile;
@@ -341,7 +341,8 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
       GC_CHECK_ARG(ctx, in->h_active_dense[a] != in->h_active_dense[b], "duplicate active tile");
   }
   for (int q = 0; q < 6; ++q) GC_CHECK_ARG(ctx, std::isfinite(h_pose6[q]), "non-finite pose");
-  const double eps_lift = h_cfg[0], eps_mass = h_cfg[1], h_tile = h_cfg[2], decay_lambda = h_cfg[3];
+  const double eps_lift = cfg->eps_lift, eps_mass = cfg->eps_mass, h_tile = cfg->h_tile,
+               decay_lambda = cfg->recency_decay_lambda;
   GC_CHECK_ARG(ctx, h_tile > 0.0, "h_tile must be > 0");
 
   const int L = map->n_lobes;

@@ -322,7 +322,7 @@ int slot_stage_imu_host(gc_pipeline* p, gc_pipeline::Slot& s, const double* h_im
 
 extern "C" {
 
-int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const double* cfg, gc_pipeline** out) {
+int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const gc_pipeline_cfg* cfg, gc_pipeline** out) {
   GC_CHECK_ARG(nullptr, ctx && dims && cfg && out, "NULL argument");
   GC_CHECK_ARG(ctx, dims->H_total > 0 && dims->h_count > 0 && dims->h_begin >= 0 &&
                         dims->h_begin + dims->h_count <= dims->H_total, "bad hypothesis shard");
@@ -332,7 +332,7 @@ int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const doub
   GC_CHECK_ARG(ctx, dims->n_in_max > 0 && dims->n_cap > 0, "point counts must be positive");
   GC_CHECK_ARG(ctx, dims->world_size >= 1 && dims->rank >= 0 && dims->rank < dims->world_size, "bad rank");
   GC_CHECK_ARG(ctx, dims->geom_hyps >= 0 && dims->geom_hyps <= 65536, "geom_hyps must be in [0, 65536]");
-  GC_CHECK_ARG(ctx, cfg[GC_PCFG_TAU] >= GC_FUSED_TAU_MIN, "tau must be >= GC_FUSED_TAU_MIN (3e-3)");
+  GC_CHECK_ARG(ctx, cfg->tau >= GC_FUSED_TAU_MIN, "tau must be >= GC_FUSED_TAU_MIN (3e-3)");
   GC_HIP(ctx, hipSetDevice(ctx->device));
   if (ctx->cu_count == 0) {
     int cus = 0;
@@ -346,15 +346,15 @@ int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const doub
   P.n_in = dims->n_in_max; P.n_cap = dims->n_cap; P.G = dims->world_size;
   P.geom_H = dims->geom_hyps;
   P.cus = ctx->cu_count;
-  P.tau = cfg[GC_PCFG_TAU]; P.o0 = cfg[GC_PCFG_ORIGIN]; P.o1 = cfg[GC_PCFG_ORIGIN + 1]; P.o2 = cfg[GC_PCFG_ORIGIN + 2];
-  P.eps_psd = cfg[GC_PCFG_EPS_PSD]; P.eps_lift = cfg[GC_PCFG_EPS_LIFT]; P.eps_mass = cfg[GC_PCFG_EPS_MASS];
-  P.lambda_ou = cfg[GC_PCFG_LAMBDA_OU]; P.c_frob = cfg[GC_PCFG_C_FROB]; P.forgetting = cfg[GC_PCFG_FORGETTING];
-  P.weight_floor = cfg[GC_PCFG_WEIGHT_FLOOR]; P.power_beta_min = cfg[GC_PCFG_POWER_BETA_MIN];
-  P.power_beta_exc_c = cfg[GC_PCFG_POWER_BETA_EXC_C]; P.power_beta_z_c = cfg[GC_PCFG_POWER_BETA_Z_C];
-  P.alpha_min = cfg[GC_PCFG_ALPHA_MIN]; P.alpha_max = cfg[GC_PCFG_ALPHA_MAX]; P.c0_cond = cfg[GC_PCFG_C0_COND];
-  P.nu_max = cfg[GC_PCFG_NU_MAX];
-  P.planar_z_ref = cfg[GC_PCFG_PLANAR_Z_REF]; P.planar_z_sigma = cfg[GC_PCFG_PLANAR_Z_SIGMA];
-  P.planar_vz_sigma = cfg[GC_PCFG_PLANAR_VZ_SIGMA]; P.gravity_scale = cfg[GC_PCFG_GRAVITY_SCALE];
+  P.tau = cfg->tau; P.o0 = cfg->origin_x; P.o1 = cfg->origin_y; P.o2 = cfg->origin_z;
+  P.eps_psd = cfg->eps_psd; P.eps_lift = cfg->eps_lift; P.eps_mass = cfg->eps_mass;
+  P.lambda_ou = cfg->lambda_ou; P.c_frob = cfg->c_frob; P.forgetting = cfg->forgetting_factor;
+  P.weight_floor = cfg->weight_floor; P.power_beta_min = cfg->power_beta_min;
+  P.power_beta_exc_c = cfg->power_beta_exc_c; P.power_beta_z_c = cfg->power_beta_z_c;
+  P.alpha_min = cfg->alpha_min; P.alpha_max = cfg->alpha_max; P.c0_cond = cfg->c0_cond;
+  P.nu_max = cfg->nu_max;
+  P.planar_z_ref = cfg->planar_z_ref; P.planar_z_sigma = cfg->planar_z_sigma;
+  P.planar_vz_sigma = cfg->planar_vz_sigma; P.gravity_scale = cfg->imu_gravity_scale;
   const int Hl = P.Hl, B = P.B, NN = 484;
   const int PL = gc::partial_len(B);
   int rc = GC_OK;

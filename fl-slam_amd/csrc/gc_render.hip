@@ -522,23 +522,24 @@ int32_t gc_fbm_at_positions(gc_ctx* ctx, int64_t n, const double* d_xy, int32_t 
 }
 
 int32_t gc_bev_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_P,
-                          const double* h_view_dirs, const double* h_cfg, const gc_bev_splats* out) {
+                          const double* h_view_dirs, const gc_bev_cfg* cfg, const gc_bev_splats* out) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, batch && h_P && h_view_dirs && h_cfg && out, "NULL argument");
+  GC_CHECK_ARG(ctx, batch && h_P && h_view_dirs && cfg && out, "NULL argument");
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
   GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
-  for (int q = 0; q < GC_BEV_CFG_LEN; ++q) GC_CHECK_ARG(ctx, fabs(h_cfg[q]) <= 1e300, "the configuration must be finite");
+  GC_CHECK_ARG(ctx, cfg_all<11>(cfg, [](double v) { return fabs(v) <= 1e300; }), "the configuration must be finite");
   for (int q = 0; q < 6 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_P[q]) <= 1e300, "P must be finite");
   for (int q = 0; q < 3 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_view_dirs[q]) <= 1e300, "view_dirs must be finite");
   BevCfg c;
-  c.ox = h_cfg[0]; c.oy = h_cfg[1]; c.ppm = h_cfg[2]; c.eps = h_cfg[3]; c.gamma = h_cfg[4]; c.logdet0 = h_cfg[5];
-  c.alpha_min = h_cfg[6]; c.octaves = (int)h_cfg[7]; c.gain = h_cfg[8]; c.seed = (int64_t)h_cfg[9]; c.s_f = h_cfg[10];
+  c.ox = cfg->origin_x; c.oy = cfg->origin_y; c.ppm = cfg->px_per_m; c.eps = cfg->eps; c.gamma = cfg->opacity_gamma;
+  c.logdet0 = cfg->logdet0; c.alpha_min = cfg->alpha_min; c.octaves = (int)cfg->fbm_octaves; c.gain = cfg->fbm_gain;
+  c.seed = (int64_t)cfg->fbm_seed; c.s_f = cfg->fbm_modulate_scale;
   GC_CHECK_ARG(ctx, c.ppm > 0.0, "px_per_m must be > 0");
-  GC_CHECK_ARG(ctx, h_cfg[7] >= 0.0 && h_cfg[7] <= 32.0 && h_cfg[7] == floor(h_cfg[7]),
+  GC_CHECK_ARG(ctx, cfg->fbm_octaves >= 0.0 && cfg->fbm_octaves <= 32.0 && cfg->fbm_octaves == floor(cfg->fbm_octaves),
                "fbm_octaves must be an integer in [0, 32]");
-  GC_CHECK_ARG(ctx, h_cfg[9] >= 0.0 && h_cfg[9] < 2147483648.0 && h_cfg[9] == floor(h_cfg[9]),
+  GC_CHECK_ARG(ctx, cfg->fbm_seed >= 0.0 && cfg->fbm_seed < 2147483648.0 && cfg->fbm_seed == floor(cfg->fbm_seed),
                "fbm_seed must be an integer in [0, 2^31)");
   if (n == 0) return GC_OK;
   GC_CHECK_ARG(ctx, batch->mu_world && batch->Sigma_world && batch->eta && batch->color, "NULL batch field");

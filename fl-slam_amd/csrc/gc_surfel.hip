@@ -384,43 +384,39 @@ using namespace gc;
 extern "C" {
 
 int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points, const double* d_timestamps,
-                                 const double* d_weights, const double* h_cfg, double* d_Lambdas, double* d_thetas,
+                                 const double* d_weights, const gc_surfel_cfg* h, double* d_Lambdas, double* d_thetas,
                                  double* d_etas, double* d_weights_out, int32_t* d_sources,
                                  int32_t* d_source_indices, uint8_t* d_valid_mask, double* d_timestamps_out,
                                  double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = gc::join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, h_cfg && h_n_valid, "NULL argument");
+  GC_CHECK_ARG(ctx, h && h_n_valid, "NULL argument");
   GC_CHECK_ARG(ctx, N >= 0 && N <= kSfMaxPoints, "N must be in [0, 4194304]");
   GC_CHECK_ARG(ctx, N == 0 || (d_points && d_timestamps && d_weights), "NULL point buffer");
   GC_CHECK_ARG(ctx, d_Lambdas && d_thetas && d_etas && d_weights_out && d_sources && d_source_indices &&
                         d_valid_mask && d_timestamps_out && d_colors, "NULL batch buffer");
-  for (int q = 0; q < GC_SURFEL_CFG_LEN; ++q) GC_CHECK_ARG(ctx, h_cfg[q] == h_cfg[q], "NaN in the configuration");
-  const auto as_int = [&](int q, double lo, double hi, int* out) {
-    if (!(h_cfg[q] >= lo && h_cfg[q] <= hi) || h_cfg[q] != floor(h_cfg[q])) return false;
-    *out = (int)h_cfg[q];
+  GC_CHECK_ARG(ctx, gc::cfg_all<17>(h, [](double v) { return v == v; }), "NaN in the configuration");
+  const auto as_int = [](double v, double lo, double hi, int* out) {
+    if (!(v >= lo && v <= hi) || v != floor(v)) return false;
+    *out = (int)v;
     return true;
   };
   SfCfg cfg;
-  GC_CHECK_ARG(ctx, as_int(0, 1, 1 << 24, &cfg.n_surfel), "n_surfel must be in [1, 2^24]");
-  GC_CHECK_ARG(ctx, as_int(1, 0, 1 << 24, &cfg.n_feat), "n_feat must be in [0, 2^24]");
-  GC_CHECK_ARG(ctx, h_cfg[2] > 0.0 && 2e5 / h_cfg[2] < 2147483648.0, "voxel_size_m must be > 0 and 2e5 / voxel_size_m < 2^31");
-  GC_CHECK_ARG(ctx, as_int(3, 1, kSfMaxCells, &cfg.n1) && as_int(4, 1, kSfMaxCells, &cfg.n2) &&
-                        as_int(5, 1, kSfMaxCells, &cfg.nz), "grid sizes must be in [1, 16384]");
+  GC_CHECK_ARG(ctx, as_int(h->n_surfel, 1, 1 << 24, &cfg.n_surfel), "n_surfel must be in [1, 2^24]");
+  GC_CHECK_ARG(ctx, as_int(h->n_feat, 0, 1 << 24, &cfg.n_feat), "n_feat must be in [0, 2^24]");
+  GC_CHECK_ARG(ctx, h->voxel_size_m > 0.0 && 2e5 / h->voxel_size_m < 2147483648.0,
+               "voxel_size_m must be > 0 and 2e5 / voxel_size_m < 2^31");
+  GC_CHECK_ARG(ctx, as_int(h->hex3d_num_cells_1, 1, kSfMaxCells, &cfg.n1) &&
+                        as_int(h->hex3d_num_cells_2, 1, kSfMaxCells, &cfg.n2) &&
+                        as_int(h->hex3d_num_cells_z, 1, kSfMaxCells, &cfg.nz), "grid sizes must be in [1, 16384]");
   const int64_t n_cells64 = (int64_t)cfg.n1 * cfg.n2 * cfg.nz;
   GC_CHECK_ARG(ctx, n_cells64 <= kSfMaxCells, "the grid must hold at most 16384 cells");
-  GC_CHECK_ARG(ctx, as_int(6, 1, kSfMaxOcc, &cfg.max_occ), "max_occupants must be in [1, 1024]");
-  GC_CHECK_ARG(ctx, as_int(7, -(1 << 24), 1 << 24, &cfg.min_points), "min_points_per_voxel out of range");
-  GC_CHECK_ARG(ctx, as_int(16, 1, 8, &cfg.n_lobes), "n_lobes must be in [1, 8]");
-  cfg.h = h_cfg[2];
-  cfg.sensor_var = h_cfg[8];
-  cfg.nu = h_cfg[9];
-  cfg.psi = h_cfg[10];
-  cfg.kappa_scale = h_cfg[11];
-  cfg.kappa_min = h_cfg[12];
-  cfg.kappa_max = h_cfg[13];
-  cfg.eig_min = h_cfg[14];
-  cfg.eps_lift = h_cfg[15];
+  GC_CHECK_ARG(ctx, as_int(h->hex3d_max_occupants, 1, kSfMaxOcc, &cfg.max_occ), "max_occupants must be in [1, 1024]");
+  GC_CHECK_ARG(ctx, as_int(h->min_points_per_voxel, -(1 << 24), 1 << 24, &cfg.min_points), "min_points_per_voxel out of range");
+  GC_CHECK_ARG(ctx, as_int(h->n_lobes, 1, 8, &cfg.n_lobes), "n_lobes must be in [1, 8]");
+  cfg.h = h->voxel_size_m; cfg.sensor_var = h->sensor_noise_var_per_axis; cfg.nu = h->wishart_nu;
+  cfg.psi = h->wishart_psi_scale; cfg.kappa_scale = h->kappa_main_scale; cfg.kappa_min = h->kappa_min;
+  cfg.kappa_max = h->kappa_max; cfg.eig_min = h->eig_min; cfg.eps_lift = h->eps_lift;
   const int n_cells = (int)n_cells64;
   const int64_t blocks = (N + kSfT - 1) / kSfT;
   const int G = (int)(blocks < 1 ? 1 : (blocks > kSfMaxGrid ? kSfMaxGrid : blocks));

@@ -321,6 +321,23 @@ def default_context() -> Context:
     return c
 
 
+def cfg(struct_name: str, values, **coded):
+    """A gc_*_cfg struct of the header (doubles only) for ctypes.byref, each member from the value of its name in
+    the dict values. A configuration object in its place gives the members it has as attributes (its other
+    attributes are ignored) and coded the rest: enumeration codes, members it names otherwise. TypeError saying
+    which member is not given, which key of values or coded is no member, which member is not a double."""
+    st = STRUCTS[struct_name]
+    names = [name for name, _ in st._fields_]
+    if not isinstance(values, dict):
+        values = {n: getattr(values, n) for n in names if hasattr(values, n)}
+    values = {**values, **coded}
+    wrong = ([f"{n} is not a double" for n, t in st._fields_ if t is not C.c_double] +
+             [f"{n} is not given" for n in names if n not in values] + [f"no member {n}" for n in values if n not in names])
+    if wrong:
+        raise TypeError(f"{struct_name}: " + "; ".join(wrong))
+    return st(*[float(values[n]) for n in names])
+
+
 def f64p(vals):
     """Host double[] for small by-value vector arguments (e.g. h_origin3)."""
     a = np.ascontiguousarray(vals, dtype=np.float64)

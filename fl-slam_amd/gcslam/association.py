@@ -135,6 +135,11 @@ class PrimitiveAssociationResult:
     device: Optional[dict] = None
 
 
+def _cfg(cfg: AssociationConfig, eps_lift: float):
+    return _abi.cfg("gc_ot_cfg", cfg, k_assoc=int(cfg.k_assoc), eps_lift=eps_lift,
+                    weight_proportional=cfg.a_policy == MeasurementMassPolicy.WEIGHT_PROPORTIONAL)
+
+
 def _p95(x: np.ndarray) -> float:
     s = np.sort(np.asarray(x).reshape(-1))
     return float(s[min(int(0.95 * s.shape[0]), s.shape[0] - 1)]) if s.shape[0] else 0.0
@@ -181,13 +186,9 @@ def associate_primitives_ot(measurement_batch, map_view: DeviceMapView, config: 
                candidate_tile_ids=_abi.DeviceArray(ctx, (N, K), np.int64),
                candidate_slots=_abi.DeviceArray(ctx, (N, K), np.int64), row_masses=_abi.DeviceArray(ctx, N),
                cost_matrix=_abi.DeviceArray(ctx, (N, K)))
-    h_cfg = np.array([K, cfg.k_sinkhorn, cfg.beta, cfg.epsilon, cfg.tau_a, cfg.tau_b, float(cfg.cost_subtract_row_min),
-                      float(cfg.a_policy == MeasurementMassPolicy.WEIGHT_PROPORTIONAL), cfg.eps_mass, cfg.h_tile,
-                      cfg.r_stencil_tiles_xy, cfg.r_stencil_tiles_z, cfg.scan_seq, cfg.recency_decay_lambda, eps_lift],
-                     np.float64)
     cert_v = np.zeros(13)
     _abi.call("gc_associate_primitives_ot", ctx.handle, N, L, dev[0].ptr, dev[1].ptr, dev[2].ptr, dev[3].ptr,
-              dev[4].ptr, C.byref(map_view.struct), h_cfg.ctypes.data, out["responsibilities"].ptr,
+              dev[4].ptr, C.byref(map_view.struct), C.byref(_cfg(cfg, eps_lift)), out["responsibilities"].ptr,
               out["candidate_pool_indices"].ptr, out["candidate_tile_ids"].ptr, out["candidate_slots"].ptr,
               out["row_masses"].ptr, out["cost_matrix"].ptr, cert_v.ctypes.data, ctx=ctx)
     res = PrimitiveAssociationResult(**{k: v.download() for k, v in out.items()}, device=out)

@@ -12,8 +12,9 @@ device is asked for."""
 
 from __future__ import annotations
 
+import ctypes as C
 import math
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -22,7 +23,7 @@ from .. import _abi
 from .camera_splats import CameraFeatures, DeviceCameraFeatures, PinholeIntrinsics, _intr_vector, _n_rows
 from .keypoint_detector import DeviceKeypoints
 
-DEPTH_SAMPLE_MODES = ("nearest", "median3", "median5", "hex")  # the codes 0..3 of the GC_CAMFEAT_CFG_LEN vector
+DEPTH_SAMPLE_MODES = ("nearest", "median3", "median5", "hex")  # the codes 0..3 of gc_camfeat_cfg.depth_sample_mode
 DEPTH_MODELS = ("linear", "quadratic")                         # the codes 0, 1
 AUX_NAMES = ("depth_sigma_c_sq", "z_m", "n_window", "n_fit", "lam_min", "K")  # the columns of aux
 MAX_RADIUS = _abi.GC_CAMFEAT_MAX_RADIUS  # gc_camfeat.hip: one lane per window pixel, (2 r + 1)^2 <= 64
@@ -33,7 +34,7 @@ MAX_PIXELS = _abi.GC_IMAGE_MAX_PIXELS
 class VisualFeatureConfig:
     """visual_feature_node.cpp:70, :74-101: the node's parameters and defaults (those of
     config/gc_unified.yaml:107-132, there with the prefix visual_feature_). The fields after
-    max_features are, in this order, the GC_CAMFEAT_CFG_LEN vector (include/gcslam.h). cov_reg_eps is
+    max_features are the members of gc_camfeat_cfg (include/gcslam.h) under the same names. cov_reg_eps is
     declared by the node and never read."""
     max_features: int = 512
     depth_sample_mode: str = "median3"
@@ -62,21 +63,18 @@ class VisualFeatureConfig:
     kappa_min: float = 0.1
 
 
-def _cfg_vector(cfg: VisualFeatureConfig) -> np.ndarray:
-    """The GC_CAMFEAT_CFG_LEN vector, checked as the device entry checks it."""
+def _cfg(cfg: VisualFeatureConfig):
+    """gc_camfeat_cfg (include/gcslam.h), checked as the device entry checks it."""
     if cfg.depth_sample_mode not in DEPTH_SAMPLE_MODES:  # the node throws (:256)
         raise ValueError(f"Unknown depth_sample_mode: {cfg.depth_sample_mode!r}; one of {DEPTH_SAMPLE_MODES}")
     if cfg.depth_model not in DEPTH_MODELS:  # :225
         raise ValueError(f"Unknown depth_model: {cfg.depth_model!r}; one of {DEPTH_MODELS}")
-    code = dict(depth_sample_mode=DEPTH_SAMPLE_MODES.index(cfg.depth_sample_mode),
-                depth_model=DEPTH_MODELS.index(cfg.depth_model))
     try:
-        h = np.array([float(code.get(f.name, getattr(cfg, f.name))) for f in fields(VisualFeatureConfig)[1:]],
-                     np.float64)
-    except (TypeError, ValueError, AttributeError) as e:
+        h = _abi.cfg("gc_camfeat_cfg", cfg, depth_sample_mode=DEPTH_SAMPLE_MODES.index(cfg.depth_sample_mode),
+                     depth_model=DEPTH_MODELS.index(cfg.depth_model))
+    except (TypeError, ValueError) as e:
         raise ValueError(f"config does not hold the VisualFeatureConfig fields: {e}") from None
-    assert h.shape[0] == _abi.GC_CAMFEAT_CFG_LEN
-    if np.isnan(h).any():
+    if np.isnan(np.frombuffer(h, np.float64)).any():
         raise ValueError("NaN in the configuration")
     for name in ("hex_radius", "quad_fit_radius"):
         r = getattr(cfg, name)
@@ -152,7 +150,7 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
     fit; a keypoint without a valid depth has xyz 0, cov_xyz invalid_cov_inflate I, weight 0,
     depth_Lambda_c = depth_theta_c = 0 and a NaN depth_sigma_c_sq."""
     cfg = config or VisualFeatureConfig()
-    h_cfg = _cfg_vector(cfg)
+    c_cfg = _cfg(cfg)
     k_max = _max_features(cfg)
     if isinstance(intrinsics, PinholeIntrinsics):
         intrinsics = (intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy)
@@ -222,6 +220,6 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
         (d_kp,) = _abi.upload_many(ctx, [np.ascontiguousarray(kp)])
     out = _abi.alloc_many(ctx, [((m,) + shp, dt) for _, shp, dt in _OUT])
     _abi.call("gc_camera_features_lift", ctx.handle, H, W, d_depth.ptr, d_rgb.ptr if d_rgb is not None else None, m,
-              d_kp.ptr, h_k.ctypes.data, h_cfg.ctypes.data, *[o.ptr for o in out], ctx=ctx)
+              d_kp.ptr, h_k.ctypes.data, C.byref(c_cfg), *[o.ptr for o in out], ctx=ctx)
     dev = DeviceCameraFeatures(**{name: o for (name, _, _), o in zip(_OUT, out)})
     return dev if device_out else dev.to_host()

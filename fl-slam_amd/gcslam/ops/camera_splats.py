@@ -10,6 +10,7 @@ libgcslam (csrc/gc_camsplat.hip); every argument error is raised here before a d
 
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass, fields
 from typing import Optional, Sequence
@@ -23,8 +24,8 @@ from ..measurement_batch import BATCH_ARRAYS, MeasurementBatch, create_empty_mea
 
 @dataclass(frozen=True)
 class LidarCameraDepthFusionConfig:
-    """lidar_camera_depth_fusion.py:29-63, the reference's fields and defaults in its order (the order
-    of the GC_CAM_CFG_LEN vector, include/gcslam.h)."""
+    """lidar_camera_depth_fusion.py:29-63, the reference's fields and defaults: the members of gc_cam_cfg
+    (include/gcslam.h) under the same names."""
     depth_fusion_weight_camera: float = 1.0
     depth_fusion_weight_lidar: float = 1.0
     gamma_lidar: float = 1.0
@@ -148,14 +149,13 @@ class CameraSplatDiagnostics:
 _EV_NAMES = ("Lambda_A", "theta_A", "Lambda_B", "theta_B", "Lambda_ell", "theta_ell", "z_B", "sigma_sq_B", "w_B")
 
 
-def _cfg_vector(cfg: LidarCameraDepthFusionConfig) -> np.ndarray:
-    """The GC_CAM_CFG_LEN vector, checked as the device entry checks it."""
+def _cfg(cfg: LidarCameraDepthFusionConfig):
+    """gc_cam_cfg (include/gcslam.h), checked as the device entry checks it."""
     try:
-        h = np.array([float(getattr(cfg, f.name)) for f in fields(LidarCameraDepthFusionConfig)], np.float64)
-    except (TypeError, ValueError, AttributeError) as e:
+        h = _abi.cfg("gc_cam_cfg", cfg)
+    except (TypeError, ValueError) as e:
         raise ValueError(f"config does not hold the LidarCameraDepthFusionConfig fields: {e}") from None
-    assert h.shape[0] == _abi.GC_CAM_CFG_LEN
-    if np.isnan(h).any():
+    if np.isnan(np.frombuffer(h, np.float64)).any():
         raise ValueError("NaN in the configuration")
     r = cfg.lidar_projection_radius_pix
     if not (r > 0.0 and math.isfinite(r)):
@@ -218,7 +218,7 @@ def lidar_depth_evidence(points_camera_frame, uv_query, fx, fy, cx, cy,
     w_B, n_in_radius. points_camera_frame (N, 3) may be a DeviceArray. point_weights must hold N values
     (the reference silently ignores another size; here that is an argument error)."""
     cfg = config or LidarCameraDepthFusionConfig()
-    h_cfg, h_k = _cfg_vector(cfg), _intr_vector(fx, fy, cx, cy)
+    c_cfg, h_k = _cfg(cfg), _intr_vector(fx, fy, cx, cy)
     n = _n_rows(points_camera_frame, 3, "points_camera_frame")
     uv = np.asarray(uv_query, dtype=np.float64)
     if uv.ndim == 1 and uv.size == 2:
@@ -238,7 +238,7 @@ def lidar_depth_evidence(points_camera_frame, uv_query, fx, fy, cx, cy,
     (duv,) = _abi.upload_many(ctx, [uv.reshape(m, 2)])
     d_ev, d_cnt = _abi.alloc_many(ctx, [((m, _abi.GC_CAM_EV), np.float64), ((m,), np.int32)])
     _abi.call("gc_lidar_depth_evidence", ctx.handle, n, dp.ptr if dp else None, m, duv.ptr, h_k.ctypes.data,
-              h_cfg.ctypes.data, dw.ptr if dw else None, d_ev.ptr, d_cnt.ptr, ctx=ctx)
+              C.byref(c_cfg), dw.ptr if dw else None, d_ev.ptr, d_cnt.ptr, ctx=ctx)
     ev, cnt = _abi.download_many([d_ev, d_cnt])
     out = {k: np.ascontiguousarray(ev[:, q]) for q, k in enumerate(_EV_NAMES)}
     if not return_diag:
@@ -364,7 +364,7 @@ def camera_measurement_batch(points_base, features, intrinsics: PinholeIntrinsic
     batch's fields and batch.device. With return_diag the result is (batch, CameraSplatDiagnostics).
     No features gives create_empty_measurement_batch, as feature_list_to_camera_batch does."""
     cfg = config or LidarCameraDepthFusionConfig()
-    h_cfg = _cfg_vector(cfg)
+    c_cfg = _cfg(cfg)
     h_k = _intr_vector(intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy)
     _check_budget(n_feat, n_surfel)
     n_feat, n_surfel = int(n_feat), int(n_surfel)
@@ -399,7 +399,7 @@ def camera_measurement_batch(points_base, features, intrinsics: PinholeIntrinsic
              ((m,), np.int32)]
     names, blk = _batch_block(ctx, n_feat + n_surfel, GC_VMF_N_LOBES, extra)
     _abi.call("gc_camera_measurement_batch", ctx.handle, n, dp.ptr if dp else None, R.ctypes.data, t.ctypes.data, m,
-              *[d.ptr for d in dev], h_k.ctypes.data, h_cfg.ctypes.data, float(pixel_sigma), float(timestamp_sec),
+              *[d.ptr for d in dev], h_k.ctypes.data, C.byref(c_cfg), float(pixel_sigma), float(timestamp_sec),
               n_feat, n_surfel, GC_VMF_N_LOBES, float(eps_lift), *[b.ptr for b in blk], ctx=ctx)
     counts = dict(n_feat=n_feat, n_surfel=n_surfel, n_camera_valid=min(m, n_feat), n_lidar_valid=0)
     batch, rest = _finish_batch(names, blk, counts, device_out)

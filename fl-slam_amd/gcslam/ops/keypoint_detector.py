@@ -28,7 +28,8 @@ MAX_PIXELS = _abi.GC_IMAGE_MAX_PIXELS
 @dataclass(frozen=True)
 class OrbDetectorConfig:
     """The arguments the node gives cv::ORB::create (visual_feature_node.cpp:149-158) and Harris's k.
-    In this order they are the GC_KP_CFG_LEN vector (include/gcslam.h)."""
+    They are the members of gc_kp_cfg (include/gcslam.h); max_features and n_levels are ORB's nfeatures and
+    nlevels there."""
     max_features: int = 512
     scale_factor: float = 1.2
     n_levels: int = 8
@@ -87,8 +88,8 @@ def _int_in(v, lo: int, hi: int, what: str) -> int:
     return int(v)
 
 
-def _cfg_vector(cfg: OrbDetectorConfig) -> np.ndarray:
-    """The GC_KP_CFG_LEN vector, checked as the device entry checks it."""
+def _cfg(cfg: OrbDetectorConfig):
+    """gc_kp_cfg (include/gcslam.h), checked as the device entry checks it."""
     try:
         k = _int_in(cfg.max_features, 1, _abi.GC_CAM_MAX_QUERIES, "max_features")
         levels = _int_in(cfg.n_levels, 1, _abi.GC_KP_MAX_LEVELS, "n_levels")
@@ -101,9 +102,8 @@ def _cfg_vector(cfg: OrbDetectorConfig) -> np.ndarray:
         raise ValueError(f"scale_factor must be finite and > 1 as float32, got {sf}")
     if not math.isfinite(hk):
         raise ValueError(f"harris_k must be finite, got {hk}")
-    h = np.array([k, sf, levels, edge, thr, hk], np.float64)
-    assert h.shape[0] == _abi.GC_KP_CFG_LEN
-    return h
+    return _abi.cfg("gc_kp_cfg", dict(nfeatures=k, scale_factor=sf, nlevels=levels, edge_threshold=edge,
+                                      fast_threshold=thr, harris_k=hk))
 
 
 def _image_shape(image):
@@ -120,13 +120,13 @@ def keypoints_plan(H: int, W: int, config: Optional[OrbDetectorConfig] = None) -
     """gc_keypoints_plan (host only): sizes [(W_l, H_l)], scales, quotas, capacities, the levels' byte
     offsets in the pyramid, pyramid_bytes and workspace_bytes."""
     cfg = config or OrbDetectorConfig()
-    h_cfg = _cfg_vector(cfg)
+    c_cfg = _cfg(cfg)
     if int(H) != H or int(W) != W or H < 1 or W < 1 or H * W > MAX_PIXELS:
         raise ValueError(f"an image of {H} x {W}; H and W must be integers >= 1 and H W <= 2^26")
     lv = np.zeros((_abi.GC_KP_MAX_LEVELS, _abi.GC_KP_PLAN_ROW), np.int64)
     sc = np.zeros(_abi.GC_KP_MAX_LEVELS, np.float64)
     nb = np.zeros(2, np.int64)
-    _abi.call("gc_keypoints_plan", int(H), int(W), h_cfg.ctypes.data, lv.ctypes.data, sc.ctypes.data, nb.ctypes.data)
+    _abi.call("gc_keypoints_plan", int(H), int(W), C.byref(c_cfg), lv.ctypes.data, sc.ctypes.data, nb.ctypes.data)
     n = int(cfg.n_levels)
     return dict(sizes=[(int(r[0]), int(r[1])) for r in lv[:n]], scales=[float(s) for s in sc[:n]],
                 quotas=[int(r[2]) for r in lv[:n]], caps=[int(r[3]) for r in lv[:n]],
@@ -156,7 +156,7 @@ def detect_keypoints(image, config: Optional[OrbDetectorConfig] = None, *, ctx=N
     list of the levels, level 0 the grey image: host (H_l, W_l) uint8 arrays, or with device_out
     DeviceArray views of the one pyramid buffer."""
     cfg = config or OrbDetectorConfig()
-    h_cfg = _cfg_vector(cfg)
+    c_cfg = _cfg(cfg)
     H, W, channels = _image_shape(image)
     if isinstance(image, _abi.DeviceArray):
         if image.dtype != np.uint8:
@@ -173,7 +173,7 @@ def detect_keypoints(image, config: Optional[OrbDetectorConfig] = None, *, ctx=N
     d_pyr = _abi.DeviceArray(ctx, (plan["pyramid_bytes"],), np.uint8)
     d_kp, d_meta, d_counts = _abi.alloc_many(ctx, [((k, 3), np.float64), ((k, 4), np.int32),
                                                    ((_abi.GC_KP_COUNTS_LEN,), np.int32)])
-    _abi.call("gc_keypoints_detect", ctx.handle, H, W, channels, d_img.ptr, h_cfg.ctypes.data, d_pyr.ptr, d_kp.ptr,
+    _abi.call("gc_keypoints_detect", ctx.handle, H, W, channels, d_img.ptr, C.byref(c_cfg), d_pyr.ptr, d_kp.ptr,
               d_meta.ptr, d_counts.ptr, ctx=ctx)
     if device_out:
         c = d_counts.download()

@@ -118,13 +118,9 @@ def extract_lidar_surfels(points, timestamps, weights, config: Optional[SurfelEx
                 _abi.call("gc_buffer_copy", ctx.handle, out[k].ptr, s.ptr, out[k].nbytes, ctx=ctx)
             else:
                 out[k].upload(np.ascontiguousarray(s).reshape(shapes[k]).astype(BATCH_ARRAYS[k][2], copy=False))
-    h_cfg = np.array([n_surfel, n_feat, cfg.voxel_size_m, cfg.hex3d_num_cells_1, cfg.hex3d_num_cells_2,
-                      cfg.hex3d_num_cells_z, cfg.hex3d_max_occupants, cfg.min_points_per_voxel,
-                      cfg.sensor_noise_var_per_axis, cfg.wishart_nu, cfg.wishart_psi_scale, cfg.kappa_main_scale,
-                      cfg.kappa_min, cfg.kappa_max, cfg.eig_min, cfg.eps_lift, n_lobes], np.float64)
-    assert h_cfg.shape[0] == _abi.GC_SURFEL_CFG_LEN
     nv = C.c_int32(0)
-    _abi.call("gc_extract_lidar_surfels", ctx.handle, n, dp.ptr, dt.ptr, dw.ptr, h_cfg.ctypes.data,
+    _abi.call("gc_extract_lidar_surfels", ctx.handle, n, dp.ptr, dt.ptr, dw.ptr,
+              C.byref(_abi.cfg("gc_surfel_cfg", cfg, n_lobes=n_lobes)),
               *[out[k].ptr for k in names], d_cells.ptr, C.byref(nv), ctx=ctx)
     n_use = int(nv.value)
     counts = dict(n_feat=n_feat, n_surfel=n_surfel, n_lidar_valid=n_use,

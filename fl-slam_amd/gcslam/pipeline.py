@@ -55,13 +55,11 @@ class PipelineConfig:
     planar_vz_sigma: float = GC_PLANAR_VZ_SIGMA
     imu_gravity_scale: float = 1.0
 
-    def as_array(self, H_total: int) -> np.ndarray:
-        floor = 0.01 / H_total if self.weight_floor is None else self.weight_floor
-        return np.array([self.tau, *self.lidar_origin, self.eps_psd, self.eps_lift, self.eps_mass,
-                         self.lambda_ou, self.c_frob, self.forgetting_factor, floor, self.power_beta_min,
-                         self.power_beta_exc_c, self.power_beta_z_c, self.alpha_min, self.alpha_max,
-                         self.c0_cond, self.nu_max, self.planar_z_ref, self.planar_z_sigma,
-                         self.planar_vz_sigma, self.imu_gravity_scale], dtype=np.float64)
+    def as_struct(self, H_total: int):
+        """gc_pipeline_cfg (include/gcslam.h) for H_total hypotheses."""
+        ox, oy, oz = self.lidar_origin
+        return _abi.cfg("gc_pipeline_cfg", self, origin_x=ox, origin_y=oy, origin_z=oz,
+                        weight_floor=0.01 / H_total if self.weight_floor is None else self.weight_floor)
 
 
 def _p(a):
@@ -92,9 +90,9 @@ class BatchedScanPipeline:
         self.rank, self.world = rank, world_size
         d = _abi.PipelineDims(H_total, self.h0, self.Hl, self.B, self.M, world_size, rank, int(geometry_hyps),
                               int(n_in_max), int(self.cfg.n_points_cap))
-        cfgv = self.cfg.as_array(H_total)
         h = C.c_void_p()
-        _abi.call("gc_pipeline_create", self.ctx.handle, C.addressof(d), cfgv.ctypes.data, C.byref(h), ctx=self.ctx)
+        _abi.call("gc_pipeline_create", self.ctx.handle, C.addressof(d), C.byref(self.cfg.as_struct(H_total)), C.byref(h),
+                  ctx=self.ctx)
         self.handle = h.value
         self._comm = None
         self._smap = None

@@ -778,10 +778,8 @@ def _maintain_check(atlas_map, dense: List[int], cfg: MapUpdateConfig) -> None:
 def _maintain_launch(atlas_map, d_dense, h_dense: np.ndarray, cfg: MapUpdateConfig, max_primitives: Optional[int],
                      max_sort_keys: int, d_stats) -> None:
     """gc_primitive_map_maintain on the map's stream: no download, no wait."""
-    h_cfg = np.array([cfg.primitive_cull_weight_threshold, cfg.primitive_forgetting_factor,
-                      cfg.primitive_merge_threshold, cfg.eps_psd, cfg.eps_lift], np.float64)
     _abi.call("gc_primitive_map_maintain", atlas_map.ctx.handle, C.byref(atlas_map.struct()), atlas_map.m_tile,
-              int(h_dense.shape[0]), d_dense.ptr, h_dense.ctypes.data, h_cfg.ctypes.data,
+              int(h_dense.shape[0]), d_dense.ptr, h_dense.ctypes.data, C.byref(_abi.cfg("gc_map_maintain_cfg", cfg)),
               -1 if max_primitives is None else int(max_primitives), int(cfg.k_merge_pairs_tile),
               int(cfg.max_tile_size), int(max_sort_keys), d_stats.ptr, ctx=atlas_map.ctx)
 
@@ -960,10 +958,9 @@ def primitive_map_update_from_association(atlas_map: DevicePrimitiveMap, associa
         s_in = _MapUpdateIn(N, m_tile, K, n_active, k_ins, int(cfg.block_size), *[d.ptr for d in d_in],
                             h_dense.ctypes.data)
         s_out = _MapUpdateOut(*[d.ptr for d in d_out[:8]])
-        h_cfg = np.array([cfg.eps_lift, cfg.eps_mass, cfg.h_tile, cfg.recency_decay_lambda], np.float64)
         _abi.call("gc_primitive_map_update", ctx.handle, C.byref(atlas_map.struct()), C.byref(s_in), pose.ctypes.data,
-                  h_cfg.ctypes.data, float(timestamp), int(scan_seq), int(atlas_map.next_global_id), C.byref(s_out),
-                  ctx=ctx)
+                  C.byref(_abi.cfg("gc_map_update_cfg", cfg)), float(timestamp), int(scan_seq),
+                  int(atlas_map.next_global_id), C.byref(s_out), ctx=ctx)
         if on_device:  # behind the last insert, on the same stream
             _maintain_launch(atlas_map, d_in[-1], h_dense, cfg, None, 0, d_out[8])
         idx, val, slots, ids, pL, pth, pw, stats, *mstats = _abi.download_many(d_out)  # the one download

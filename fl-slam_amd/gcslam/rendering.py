@@ -30,7 +30,7 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _abi
-from ._abi import GC_BEV_CFG_LEN, GC_CAMVIEW_CFG_LEN, GC_RENDER_MAX_CAP, GC_RENDER_MAX_TILE, GC_RENDER_MAX_VIEWS
+from ._abi import GC_RENDER_MAX_CAP, GC_RENDER_MAX_TILE, GC_RENDER_MAX_VIEWS
 from .association import DeviceMapView, extract_atlas_map_view
 from .constants import GC_EPS_LIFT
 from .ops.camera_splats import PinholeIntrinsics
@@ -241,13 +241,11 @@ def _check_raster_args(tile_size, height, width, cap, n) -> None:
         raise ValueError(f"a negative splat count {n}")
 
 
-def _bev_cfg_vector(viewport: Viewport, cfg: SplatRenderingConfig, fbm_seed, fbm_modulate_scale) -> np.ndarray:
-    ox, oy = (float(v) for v in viewport.origin_xy)
-    h = np.array([ox, oy, float(viewport.px_per_m), float(cfg.eps), float(cfg.opacity_gamma), float(cfg.logdet0),
-                  float(cfg.alpha_min), float(cfg.fbm_octaves), float(cfg.fbm_gain), float(fbm_seed),
-                  float(fbm_modulate_scale)], np.float64)
-    assert h.shape[0] == GC_BEV_CFG_LEN
-    if not np.isfinite(h).all():
+def _bev_cfg(viewport: Viewport, cfg: SplatRenderingConfig, fbm_seed, fbm_modulate_scale):
+    ox, oy = viewport.origin_xy
+    h = _abi.cfg("gc_bev_cfg", cfg, origin_x=ox, origin_y=oy, px_per_m=viewport.px_per_m, fbm_seed=fbm_seed,
+                 fbm_modulate_scale=fbm_modulate_scale)
+    if not np.isfinite(np.frombuffer(h, np.float64)).all():
         raise ValueError("the viewport and the rendering configuration must be finite")
     if not viewport.px_per_m > 0.0:
         raise ValueError(f"px_per_m must be > 0, got {viewport.px_per_m}")
@@ -279,7 +277,7 @@ def bev_splat_prep(batch: DeviceRenderableBatch, viewport: Viewport, P, view_dir
     means_px (n_views, n, 2), Sigmas_inv (n_views, n, 2, 2), alphas (n_views, n), colors
     (n_views, n, 3), fbm (n), and with with_sigma_bev Sigmas_bev (n_views, n, 2, 2). No wait."""
     cfg = render_cfg or SplatRenderingConfig()
-    h_cfg = _bev_cfg_vector(viewport, cfg, fbm_seed, fbm_modulate_scale)
+    c_cfg = _bev_cfg(viewport, cfg, fbm_seed, fbm_modulate_scale)
     P = np.ascontiguousarray(P, np.float64)
     if P.ndim == 2:
         P = P[None]
@@ -297,7 +295,7 @@ def bev_splat_prep(batch: DeviceRenderableBatch, viewport: Viewport, P, view_dir
     out = dict(zip(names, _abi.alloc_many(ctx, [shapes[k] for k in names])))
     st = _SplatStruct(*[out[k].ptr if k in out else None for k, _ in _SplatStruct._fields_])
     _abi.call("gc_bev_splat_prep", ctx.handle, C.byref(batch.struct), n, nv, P.ctypes.data, vd.ctypes.data,
-              h_cfg.ctypes.data, C.byref(st), ctx=ctx)
+              C.byref(c_cfg), C.byref(st), ctx=ctx)
     return out
 
 
@@ -338,7 +336,7 @@ def render_map_bev(batch_or_map: Union[DeviceRenderableBatch, RenderablePrimitiv
     cfg, bcfg = render_cfg or SplatRenderingConfig(), bev_cfg or BEVPushforwardConfig()
     H, W = viewport.height, viewport.width
     _check_raster_args(cfg.tile_size, H, W, cfg.max_splats_per_tile, 0)
-    _bev_cfg_vector(viewport, cfg, fbm_seed, fbm_modulate_scale)
+    _bev_cfg(viewport, cfg, fbm_seed, fbm_modulate_scale)
     P, vd = bev_views(bcfg, views)
     if isinstance(batch_or_map, DevicePrimitiveMap):
         batch = publish_renderable(batch_or_map)
@@ -425,14 +423,12 @@ def camera_from_world(pose, R_base_camera=None, t_base_camera=None, *, ctx=None)
     return T
 
 
-def _cam_cfg_vector(cfg: CameraViewConfig) -> np.ndarray:
+def _camview_cfg(cfg: CameraViewConfig):
     bg = np.asarray(cfg.background, np.float64).reshape(-1)
     if bg.shape != (3,):
         raise ValueError(f"background must hold 3 values, got {cfg.background!r}")
-    h = np.array([cfg.near, cfg.far, cfg.lowpass_px2, cfg.radius_sigma, cfg.alpha_floor, cfg.alpha_max, cfg.alpha_skip,
-                  cfg.t_stop, bg[0], bg[1], bg[2], 1.0 if cfg.shade else 0.0, cfg.eps], np.float64)
-    assert h.shape[0] == GC_CAMVIEW_CFG_LEN
-    if not np.isfinite(h).all():
+    h = _abi.cfg("gc_camview_cfg", cfg, bg_r=bg[0], bg_g=bg[1], bg_b=bg[2], shade=bool(cfg.shade))
+    if not np.isfinite(np.frombuffer(h, np.float64)).all():
         raise ValueError("the camera view configuration must be finite")
     if not (cfg.near > 0.0 and cfg.far > cfg.near):
         raise ValueError(f"near must be > 0 and far > near, got near = {cfg.near}, far = {cfg.far}")
@@ -469,12 +465,12 @@ def _cam_views(intrinsics, T_cw) -> Tuple[np.ndarray, np.ndarray]:
 
 def _check_camera_args(intrinsics, T_cw, height, width, cfg: CameraViewConfig, n: int):
     _check_raster_args(cfg.tile_size, height, width, cfg.max_splats_per_tile, n)
-    h_cfg = _cam_cfg_vector(cfg)
+    c_cfg = _camview_cfg(cfg)
     T, K = _cam_views(intrinsics, T_cw)
     tiles = (int(height) // int(cfg.tile_size)) * (int(width) // int(cfg.tile_size))
     if T.shape[0] * tiles * n >= 1 << 32:
         raise ValueError(f"n_views * tiles * n = {T.shape[0] * tiles * n} must be below 2^32")
-    return h_cfg, T, K
+    return c_cfg, T, K
 
 
 def camera_splat_prep(batch: DeviceRenderableBatch, intrinsics, T_cw, height: int, width: int,
@@ -485,7 +481,7 @@ def camera_splat_prep(batch: DeviceRenderableBatch, intrinsics, T_cw, height: in
     PinholeIntrinsics or one per view; T_cw (4, 4) or (n_views, 4, 4) (camera_from_world). No wait."""
     cfg = cfg or CameraViewConfig()
     n, ctx = batch.count, batch.ctx
-    h_cfg, T, K = _check_camera_args(intrinsics, T_cw, height, width, cfg, n)
+    c_cfg, T, K = _check_camera_args(intrinsics, T_cw, height, width, cfg, n)
     nv = T.shape[0]
     names = [k for k, _ in _CamSplatStruct._fields_]
     specs = dict(means_px=((nv, n, 2), np.float64), Sigmas_inv=((nv, n, 2, 2), np.float64), depths=((nv, n), np.float64),
@@ -494,7 +490,7 @@ def camera_splat_prep(batch: DeviceRenderableBatch, intrinsics, T_cw, height: in
     out = dict(zip(names, _abi.alloc_many(ctx, [specs[k] for k in names])))
     st = _CamSplatStruct(*[out[k].ptr for k in names])
     _abi.call("gc_camera_splat_prep", ctx.handle, C.byref(batch.struct), n, nv, T.ctypes.data, K.ctypes.data, int(height),
-              int(width), h_cfg.ctypes.data, C.byref(st), ctx=ctx)
+              int(width), C.byref(c_cfg), C.byref(st), ctx=ctx)
     return out
 
 
@@ -507,7 +503,7 @@ def render_depth_tiles(splats: Dict[str, _abi.DeviceArray], height: int, width: 
     cfg = cfg or CameraViewConfig()
     nv, n = splats["depths"].shape
     _check_raster_args(cfg.tile_size, height, width, cfg.max_splats_per_tile, n)
-    h_cfg = _cam_cfg_vector(cfg)
+    c_cfg = _camview_cfg(cfg)
     if not 1 <= nv <= GC_RENDER_MAX_VIEWS:
         raise ValueError(f"{nv} views; between 1 and {GC_RENDER_MAX_VIEWS} are supported")
     ts, H, W, cap = int(cfg.tile_size), int(height), int(width), int(cfg.max_splats_per_tile)
@@ -520,7 +516,7 @@ def render_depth_tiles(splats: Dict[str, _abi.DeviceArray], height: int, width: 
                                    ((nv, H, W), np.int32), ((nv, T), np.int32), ((nv, T), np.int32),
                                    ((nv, T, cap), np.int32)])
     st = _CamSplatStruct(*[splats[k].ptr for k, _ in _CamSplatStruct._fields_])
-    _abi.call("gc_render_depth_tiles", ctx.handle, nv, n, C.byref(st), H, W, ts, cap, h_cfg.ctypes.data,
+    _abi.call("gc_render_depth_tiles", ctx.handle, nv, n, C.byref(st), H, W, ts, cap, C.byref(c_cfg),
               *[a.ptr for a in arrays], ctx=ctx)
     return dict(zip(names, arrays))
 

@@ -223,28 +223,33 @@ typedef struct {
   int64_t n_cap;     /* N_POINTS_CAP */
 } gc_pipeline_dims;
 
-/* configuration doubles (PipelineConfig, pipeline.py:96-160; constants.py) */
-#define GC_PCFG_TAU 0
-#define GC_PCFG_ORIGIN 1 /* 3: lidar origin in the base frame */
-#define GC_PCFG_EPS_PSD 4
-#define GC_PCFG_EPS_LIFT 5
-#define GC_PCFG_EPS_MASS 6
-#define GC_PCFG_LAMBDA_OU 7
-#define GC_PCFG_C_FROB 8
-#define GC_PCFG_FORGETTING 9
-#define GC_PCFG_WEIGHT_FLOOR 10
-#define GC_PCFG_POWER_BETA_MIN 11
-#define GC_PCFG_POWER_BETA_EXC_C 12
-#define GC_PCFG_POWER_BETA_Z_C 13
-#define GC_PCFG_ALPHA_MIN 14
-#define GC_PCFG_ALPHA_MAX 15
-#define GC_PCFG_C0_COND 16
-#define GC_PCFG_NU_MAX 17
-#define GC_PCFG_PLANAR_Z_REF 18    /* GC_PLANAR_Z_REF (constants.py:294) */
-#define GC_PCFG_PLANAR_Z_SIGMA 19  /* GC_PLANAR_Z_SIGMA (constants.py:305) */
-#define GC_PCFG_PLANAR_VZ_SIGMA 20 /* GC_PLANAR_VZ_SIGMA (constants.py:310) */
-#define GC_PCFG_GRAVITY_SCALE 21   /* PipelineConfig.imu_gravity_scale (pipeline.py:141) */
-#define GC_PCFG_LEN 22
+/* The pipeline's configuration (PipelineConfig, pipeline.py:96-160; constants.py). Like every gc_*_cfg
+ * below it holds doubles only, so it has no padding and a caller may fill it as a double array in member
+ * order. */
+typedef struct {
+  double tau;
+  double origin_x; /* the lidar origin in the base frame */
+  double origin_y;
+  double origin_z;
+  double eps_psd;
+  double eps_lift;
+  double eps_mass;
+  double lambda_ou;
+  double c_frob;
+  double forgetting_factor;
+  double weight_floor;
+  double power_beta_min;
+  double power_beta_exc_c;
+  double power_beta_z_c;
+  double alpha_min;
+  double alpha_max;
+  double c0_cond;
+  double nu_max;
+  double planar_z_ref;      /* GC_PLANAR_Z_REF (constants.py:294) */
+  double planar_z_sigma;    /* GC_PLANAR_Z_SIGMA (constants.py:305) */
+  double planar_vz_sigma;   /* GC_PLANAR_VZ_SIGMA (constants.py:310) */
+  double imu_gravity_scale; /* PipelineConfig.imu_gravity_scale (pipeline.py:141) */
+} gc_pipeline_cfg;
 
 #define GC_PIPE_MAX_SLOTS 8
 /* map bin record (B x 26): [S_dir 3, S_dir_scatter 9, N_dir, N_pos, sum_p 3, sum_ppT 9] */
@@ -268,7 +273,7 @@ typedef struct {
  *  the stored combined L on demand (one extra launch, off the scan path). */
 #define GC_COMB_LEN (484 + 22 + 22 + 6 + 16)
 
-int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const double* h_cfg, gc_pipeline** out);
+int32_t gc_pipeline_create(gc_ctx* ctx, const gc_pipeline_dims* dims, const gc_pipeline_cfg* cfg, gc_pipeline** out);
 int32_t gc_pipeline_destroy(gc_pipeline* p);
 int32_t gc_pipeline_set_bins(gc_pipeline* p, const double* h_bins);
 int32_t gc_pipeline_set_beliefs(gc_pipeline* p, const double* h_X, const double* h_z, const double* h_L,
@@ -926,20 +931,24 @@ typedef struct gc_map_update_out {
    (tiling.py:126-145); per active tile the first k_insert rows of a stable descending sort of the
    in-tile scores (others -1e30), valid_new = in_tile & score > -1e20 or all ones when none is, the
    proposals pushed to the world frame and inserted as gc_primitive_map_insert_masked does, tiles in
-   the given order on the map the fuse left, global ids running on from next_global_id.
-   h_cfg (host) = [eps_lift, eps_mass, h_tile, recency_decay_lambda]. Nothing is downloaded and the
-   stream is not waited for: the caller reads the outputs after its own download. */
+   the given order on the map the fuse left, global ids running on from next_global_id. Nothing is
+   downloaded and the stream is not waited for: the caller reads the outputs after its own download. */
+typedef struct {
+  double eps_lift;
+  double eps_mass;
+  double h_tile;
+  double recency_decay_lambda;
+} gc_map_update_cfg;
 int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const gc_map_update_in* in,
-                                const double* h_pose6, const double* h_cfg, double timestamp, int64_t scan_seq,
-                                int64_t next_global_id, const gc_map_update_out* out);
+                                const double* h_pose6, const gc_map_update_cfg* cfg, double timestamp,
+                                int64_t scan_seq, int64_t next_global_id, const gc_map_update_out* out);
 
 /* The maintenance of step 12b (backend/pipeline.py:1412-1447) over all active tiles in one pass:
    per active tile primitive_map_cull (primitive_map.py:1175-1305), primitive_map_forget (:1314-1390)
    and primitive_map_merge_reduce (:1809-2030), with the results of the per-tile entries above run in
    that order on each tile. Tile a is the slot range [dense[a] * m_tile, (dense[a] + 1) * m_tile);
    d_active_dense (device) and h_active_dense (host) hold the same n_active distinct dense tiles, each
-   in [0, m_slots / m_tile). h_cfg (host) = [weight_threshold, forgetting_factor, merge_threshold,
-   eps_psd, eps_lift]; max_primitives < 0 = no cap on the survivors.
+   in [0, m_slots / m_tile). max_primitives < 0 = no cap on the survivors.
 
    What the per-tile entries decide on the host after a download is decided here per tile on the
    device: whether the tile takes the max_primitives branch (one segmented descending sort of
@@ -967,9 +976,16 @@ int32_t gc_primitive_map_update(gc_ctx* ctx, const gc_primitive_map* map, const 
 #define GC_MAP_MAINTAIN_MERGE_CAPPED 2
 #define GC_MAP_MAINTAIN_SORT_KEYS (1 << 23)
 #define GC_MAP_MAINTAIN_GROUP_TILES 4096
+typedef struct {
+  double primitive_cull_weight_threshold;
+  double primitive_forgetting_factor;
+  double primitive_merge_threshold;
+  double eps_psd;
+  double eps_lift;
+} gc_map_maintain_cfg;
 int32_t gc_primitive_map_maintain(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, int32_t n_active,
                                   const int32_t* d_active_dense, const int32_t* h_active_dense,
-                                  const double* h_cfg, int64_t max_primitives, int32_t max_pairs,
+                                  const gc_map_maintain_cfg* cfg, int64_t max_primitives, int32_t max_pairs,
                                   int64_t max_tile_size, int64_t max_sort_keys, double* d_stats);
 
 /* primitive_map_recency_inflate (primitive_map.py:1400-1490) over a list of tiles in one pass: what
@@ -1043,9 +1059,24 @@ typedef struct gc_map_view {
 int32_t gc_extract_map_view(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_tile, const int64_t* h_dense_tiles,
                             const int64_t* h_tile_ids, double eps_lift, double eps_mass, const gc_map_view* view);
 
-#define GC_OT_CFG_LEN 15  /* [k_assoc, k_sinkhorn, beta, epsilon, tau_a, tau_b, cost_subtract_row_min,
-                             weight_proportional, eps_mass, h_tile, r_stencil_xy, r_stencil_z, scan_seq,
-                             recency_decay_lambda, eps_lift] (AssociationConfig, primitive_association.py:205-236) */
+/* AssociationConfig (primitive_association.py:205-236) and the call's eps_lift */
+typedef struct {
+  double k_assoc;
+  double k_sinkhorn;
+  double beta;
+  double epsilon;
+  double tau_a;
+  double tau_b;
+  double cost_subtract_row_min; /* 0 or 1 */
+  double weight_proportional;   /* 1: a_policy WEIGHT_PROPORTIONAL, 0: UNIFORM */
+  double eps_mass;
+  double h_tile;
+  double r_stencil_tiles_xy;
+  double r_stencil_tiles_z;
+  double scan_seq;
+  double recency_decay_lambda;
+  double eps_lift;
+} gc_ot_cfg;
 #define GC_OT_CERT_LEN 13 /* [marginal_defect_a, marginal_defect_b, transport_mass_total, sum_a, sum_b, sum_m,
                              sum_novel, ess_ot, nonzero_a, nonzero_b, total_cost, n_valid_meas, n_valid_map] */
 /* associate_primitives_ot (operators/primitive_association.py:239-553): N measurement primitives
@@ -1055,7 +1086,7 @@ int32_t gc_extract_map_view(gc_ctx* ctx, const gc_primitive_map* map, int64_t m_
    valid measurement or map entry every output is zero and n_valid_* tell which. */
 int32_t gc_associate_primitives_ot(gc_ctx* ctx, int64_t N, int32_t n_lobes, const double* d_Lambdas,
                                    const double* d_thetas, const double* d_etas, const double* d_weights,
-                                   const uint8_t* d_valid, const gc_map_view* view, const double* h_cfg,
+                                   const uint8_t* d_valid, const gc_map_view* view, const gc_ot_cfg* cfg,
                                    double* d_resp_out, int32_t* d_cand_out, int64_t* d_cand_tile_out,
                                    int64_t* d_cand_slot_out, double* d_row_mass_out, double* d_cost_out,
                                    double* h_cert_out);
@@ -1095,17 +1126,33 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
                                 double eps_mass, double* d_L_pose, double* d_h_pose, double* d_parts,
                                 double* h_cert);
 
-#define GC_SURFEL_CFG_LEN 17
+/* SurfelExtractionConfig (operators/lidar_surfel_extraction.py:43-62), then the lobes per row (GC_VMF_N_LOBES) */
+typedef struct {
+  double n_surfel;
+  double n_feat;
+  double voxel_size_m;
+  double hex3d_num_cells_1;
+  double hex3d_num_cells_2;
+  double hex3d_num_cells_z;
+  double hex3d_max_occupants;
+  double min_points_per_voxel;
+  double sensor_noise_var_per_axis;
+  double wishart_nu;
+  double wishart_psi_scale;
+  double kappa_main_scale;
+  double kappa_min;
+  double kappa_max;
+  double eig_min;
+  double eps_lift;
+  double n_lobes;
+} gc_surfel_cfg;
 #define GC_SURFEL_MAX_POINTS (1 << 22)  /* N */
 #define GC_SURFEL_MAX_CELLS 16384       /* each grid size, and the cells in all: cell keys are below 2^14 */
 #define GC_SURFEL_MAX_OCCUPANTS 1024    /* hex3d_max_occupants: bucket slots per cell */
 /* extract_lidar_surfels (operators/lidar_surfel_extraction.py:219-431; MA-hex hash grid
    common/ma_hex_web.py:221-303; batch rows structures/measurement_batch.py:262-347): the LiDAR
    slice of a MeasurementBatch from the N deskewed points (N, 3), timestamps (N) and weights (N) of
-   one scan (device). h_cfg (host) = [n_surfel, n_feat, voxel_size_m, hex3d_num_cells_1,
-   hex3d_num_cells_2, hex3d_num_cells_z, hex3d_max_occupants, min_points_per_voxel,
-   sensor_noise_var_per_axis, wishart_nu, wishart_psi_scale, kappa_main_scale, kappa_min, kappa_max,
-   eig_min, eps_lift, n_lobes] (SurfelExtractionConfig :43-62 and GC_VMF_N_LOBES).
+   one scan (device); cfg (host) is gc_surfel_cfg.
    Outputs (device, caller-allocated, n_total = n_feat + n_surfel rows): Lambdas (n_total, 3, 3),
    thetas (n_total, 3), etas (n_total, n_lobes, 3), weights (n_total), sources int32 (n_total),
    source_indices int32 (n_total), valid_mask uint8 (n_total), timestamps (n_total), colors
@@ -1120,21 +1167,37 @@ int32_t gc_visual_pose_evidence(gc_ctx* ctx, int64_t N, int32_t K, int32_t n_lob
    than 16384 cells in all, max_occupants outside [1, 1024], n_surfel < 1, voxel_size_m <= 0 or
    2e5 / voxel_size_m >= 2^31, n_lobes outside [1, 8], or NULL pointers. */
 int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points, const double* d_timestamps,
-                                 const double* d_weights, const double* h_cfg, double* d_Lambdas, double* d_thetas,
+                                 const double* d_weights, const gc_surfel_cfg* cfg, double* d_Lambdas, double* d_thetas,
                                  double* d_etas, double* d_weights_out, int32_t* d_sources,
                                  int32_t* d_source_indices, uint8_t* d_valid_mask, double* d_timestamps_out,
                                  double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid);
 
-#define GC_CAM_CFG_LEN 23    /* LidarCameraDepthFusionConfig in field order
-                                (frontend/sensors/lidar_camera_depth_fusion.py:29-63):
-                                [depth_fusion_weight_camera, depth_fusion_weight_lidar, gamma_lidar,
-                                lidar_projection_radius_pix, lidar_plane_fit_min_points,
-                                lidar_depth_base_sigma_m, lidar_incidence_sigma_scale, depth_var_min_m2,
-                                point_support_n0, point_support_alpha, spread_mad_beta, repr_gamma,
-                                lidar_ray_plane_fit_max_points, plane_intersection_delta,
-                                plane_angle_sigmoid_alpha, plane_angle_sigmoid_t, plane_planarity_sigmoid_beta,
-                                plane_planarity_rho0, plane_residual_exp_gamma, plane_fit_eps, depth_min_m,
-                                depth_sigma_max_sq, depth_min_sigmoid_alpha_z] */
+/* LidarCameraDepthFusionConfig in field order (frontend/sensors/lidar_camera_depth_fusion.py:29-63) */
+typedef struct {
+  double depth_fusion_weight_camera;
+  double depth_fusion_weight_lidar;
+  double gamma_lidar;
+  double lidar_projection_radius_pix;
+  double lidar_plane_fit_min_points;
+  double lidar_depth_base_sigma_m;
+  double lidar_incidence_sigma_scale; /* the reference never reads it */
+  double depth_var_min_m2;
+  double point_support_n0;
+  double point_support_alpha;
+  double spread_mad_beta;
+  double repr_gamma;
+  double lidar_ray_plane_fit_max_points;
+  double plane_intersection_delta;
+  double plane_angle_sigmoid_alpha;
+  double plane_angle_sigmoid_t;
+  double plane_planarity_sigmoid_beta;
+  double plane_planarity_rho0;
+  double plane_residual_exp_gamma;
+  double plane_fit_eps;
+  double depth_min_m;
+  double depth_sigma_max_sq;
+  double depth_min_sigmoid_alpha_z;
+} gc_cam_cfg;
 #define GC_CAM_EV 9          /* per query: Lambda_A theta_A Lambda_B theta_B Lambda_ell theta_ell, then Route
                                 B's z*, sigma^2 and w (NaN, NaN, 0 where Route B does not run) */
 #define GC_CAM_MAX_NEAR 1024 /* in-radius LiDAR points one query can hold */
@@ -1145,7 +1208,7 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
 /* lidar_depth_evidence (frontend/sensors/lidar_camera_depth_fusion.py:389-442; _project_camera :80-96,
    Route A :99-164, Route B :242-386, _fit_plane_weighted :207-239): the LiDAR depth evidence of M
    query pixels d_uv (M, 2) from N points in the camera frame (N, 3). h_intrinsics (host) = [fx, fy,
-   cx, cy]; h_cfg (host) = GC_CAM_CFG_LEN values; d_point_weights (N; may be NULL: uniform) weighs
+   cx, cy]; cfg (host) is gc_cam_cfg; d_point_weights (N; may be NULL: uniform) weighs
    Route B's plane fit. Outputs (device, caller-allocated): d_evidence (M, GC_CAM_EV) and d_counts
    int32 (M), the number of z > 0 points whose projection lies within the radius of the query. The
    candidates of a query are taken in ascending point index, the k_use nearest the ray by (distance,
@@ -1155,7 +1218,7 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
    non-finite intrinsics or fx, fy = 0, NULL pointers, or a query with more than GC_CAM_MAX_NEAR
    points within its radius (the outputs are then not to be used; the reference has no such cap). */
 int32_t gc_lidar_depth_evidence(gc_ctx* ctx, int64_t N, const double* d_points_cam, int64_t M, const double* d_uv,
-                                const double* h_intrinsics, const double* h_cfg, const double* d_point_weights,
+                                const double* h_intrinsics, const gc_cam_cfg* cfg, const double* d_point_weights,
                                 double* d_evidence, int32_t* d_counts);
 
 /* The camera half of a scan's MeasurementBatch in one call (backend/backend_node.py:1872-1925):
@@ -1179,7 +1242,7 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                                     const double* d_theta_c, const double* d_weight, const double* d_kappa,
                                     const double* d_mu_app, const uint8_t* d_has_mu_app, const double* d_color,
                                     const uint8_t* d_has_color, const double* d_xyz, const double* d_cov_xyz,
-                                    const double* h_intrinsics, const double* h_cfg, double pixel_sigma,
+                                    const double* h_intrinsics, const gc_cam_cfg* cfg, double pixel_sigma,
                                     double timestamp_sec, int32_t n_feat, int32_t n_surfel, int32_t n_lobes,
                                     double eps_lift, double* d_Lambdas, double* d_thetas, double* d_etas,
                                     double* d_weights_out, int32_t* d_sources, int32_t* d_source_indices,
@@ -1187,14 +1250,33 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
                                     double* d_fused_xyz, double* d_fused_cov, uint8_t* d_fused_flag,
                                     double* d_evidence, int32_t* d_counts);
 
-#define GC_CAMFEAT_CFG_LEN 24 /* the visual feature node's parameters in the order it declares them
-                                 (src/visual_feature_node.cpp:74-101): [depth_sample_mode (0 nearest,
-                                 1 median3, 2 median5, 3 hex), pixel_sigma, depth_model (0 linear,
-                                 1 quadratic), depth_sigma0, depth_sigma_slope, min_depth_m, max_depth_m,
-                                 depth_validity_slope, response_soft_scale, depth_scale, cov_reg_eps,
-                                 invalid_cov_inflate, hex_radius, quad_fit_radius, quad_fit_min_points,
-                                 quad_fit_lstsq_eps, student_t_nu, student_t_w_min, ma_tau,
-                                 ma_delta_inflate, kappa0, kappa_alpha, kappa_max, kappa_min] */
+/* The visual feature node's parameters in the order it declares them (src/visual_feature_node.cpp:74-101) */
+typedef struct {
+  double depth_sample_mode; /* 0 nearest, 1 median3, 2 median5, 3 hex */
+  double pixel_sigma;
+  double depth_model;       /* 0 linear, 1 quadratic */
+  double depth_sigma0;
+  double depth_sigma_slope;
+  double min_depth_m;
+  double max_depth_m;
+  double depth_validity_slope;
+  double response_soft_scale;
+  double depth_scale;
+  double cov_reg_eps;       /* declared by the node and never read */
+  double invalid_cov_inflate;
+  double hex_radius;
+  double quad_fit_radius;
+  double quad_fit_min_points;
+  double quad_fit_lstsq_eps;
+  double student_t_nu;
+  double student_t_w_min;
+  double ma_tau;
+  double ma_delta_inflate;
+  double kappa0;
+  double kappa_alpha;
+  double kappa_max;
+  double kappa_min;
+} gc_camfeat_cfg;
 #define GC_CAMFEAT_AUX 6      /* per keypoint: depth_sigma_c_sq (NaN without a valid depth), z_m (NaN
                                  without), the depth window's valid count, the quadratic fit's point
                                  count (0 without a valid depth), lam_min and K (0 without a fit) */
@@ -1211,7 +1293,7 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
    quadratic_fit (:401-491: the window about the rounded pixel, coordinates relative to the keypoint,
    normal equations with the ridge quad_fit_lstsq_eps solved by an unpivoted LDL^T), backproject and
    backprojection_cov (:371-399) and the assembly (:547-634). h_intrinsics (host) = [fx, fy, cx, cy];
-   h_cfg (host) = GC_CAMFEAT_CFG_LEN values. Outputs (device, caller-allocated), laid out as
+   cfg (host) is gc_camfeat_cfg. Outputs (device, caller-allocated), laid out as
    gc_camera_measurement_batch reads its feature arguments: d_uv (M, 2), d_Lambda_c, d_theta_c,
    d_weight, d_kappa (M), d_mu_app (M, 3; the normal over (norm + 1e-12), 0 without a fit),
    d_has_mu_app (uint8; the rows with a fit), d_color (M, 3), d_has_color (uint8), d_xyz (M, 3),
@@ -1220,17 +1302,24 @@ int32_t gc_camera_measurement_batch(gc_ctx* ctx, int64_t N, const double* d_poin
    and Lambda_c = theta_c = 0. One wavefront per keypoint, every sum in a fixed order, no atomics: the
    outputs are bitwise reproducible. No wait. GC_ERR_ARG for M outside [0, 4096], H or W < 1 or
    H W > 2^26, max(1, hex_radius) or max(1, quad_fit_radius) outside [1, 3], quad_fit_min_points < 1,
-   an unknown mode or model code, non-finite intrinsics or fx, fy = 0, NaN in h_cfg, or NULL pointers
+   an unknown mode or model code, non-finite intrinsics or fx, fy = 0, NaN in cfg, or NULL pointers
    (d_rgb excepted). */
 int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* d_depth, const uint8_t* d_rgb,
-                                int64_t M, const double* d_kp, const double* h_intrinsics, const double* h_cfg,
+                                int64_t M, const double* d_kp, const double* h_intrinsics, const gc_camfeat_cfg* cfg,
                                 double* d_uv, double* d_Lambda_c, double* d_theta_c, double* d_weight,
                                 double* d_kappa, double* d_mu_app, uint8_t* d_has_mu_app, double* d_color,
                                 uint8_t* d_has_color, double* d_xyz, double* d_cov_xyz, double* d_aux);
 
-#define GC_KP_CFG_LEN 6     /* [nfeatures, scale_factor, nlevels, edge_threshold, fast_threshold, harris_k]: the
-                               arguments of the node's cv::ORB::create (src/visual_feature_node.cpp:149-158;
-                               512, 1.2, 8, 31, 20) and Harris's k (0.04) */
+/* The arguments of the node's cv::ORB::create (src/visual_feature_node.cpp:149-158; 512, 1.2, 8, 31, 20) and
+   Harris's k (0.04) */
+typedef struct {
+  double nfeatures;
+  double scale_factor;
+  double nlevels;
+  double edge_threshold;
+  double fast_threshold;
+  double harris_k;
+} gc_kp_cfg;
 #define GC_KP_MAX_LEVELS 16
 #define GC_KP_PLAN_ROW 5    /* per level: W_l, H_l, the quota n_l, the candidate capacity
                                ceil(W_l / 2) ceil(H_l / 2), the level's byte offset in the pyramid */
@@ -1244,7 +1333,7 @@ int32_t gc_camera_features_lift(gc_ctx* ctx, int32_t H, int32_t W, const float* 
    uint8 on a 256-byte boundary). h_levels (GC_KP_MAX_LEVELS, GC_KP_PLAN_ROW) and h_scales
    (GC_KP_MAX_LEVELS), zero from nlevels on; h_bytes = [pyramid bytes, workspace bytes (the context's
    scratch a call carves)]. GC_ERR_ARG as gc_keypoints_detect. */
-int32_t gc_keypoints_plan(int32_t H, int32_t W, const double* h_cfg, int64_t* h_levels, double* h_scales,
+int32_t gc_keypoints_plan(int32_t H, int32_t W, const gc_kp_cfg* cfg, int64_t* h_levels, double* h_scales,
                           int64_t* h_bytes);
 
 /* Test entry (host only), in the manner of gc_test_bounded_wait: the index and weight table of one axis
@@ -1273,7 +1362,7 @@ int32_t gc_keypoints_resize_table(int64_t n_src, int64_t n_dst, int32_t* h_i0, i
    fast_threshold outside [1, 254], edge_threshold outside [4, 1024] (4 keeps the Harris reads inside
    the image), a non-finite harris_k, a non-integer count, or NULL pointers. */
 int32_t gc_keypoints_detect(gc_ctx* ctx, int32_t H, int32_t W, int32_t channels, const uint8_t* d_image,
-                            const double* h_cfg, uint8_t* d_pyramid, double* d_kp, int32_t* d_meta,
+                            const gc_kp_cfg* cfg, uint8_t* d_pyramid, double* d_kp, int32_t* d_meta,
                             int32_t* d_counts);
 
 /* measurement_batch_from_camera_splats (backend/structures/measurement_batch.py:165-259): rows
@@ -1321,9 +1410,20 @@ typedef struct gc_render_batch {
 int32_t gc_renderable_batch_from_view(gc_ctx* ctx, const gc_map_view* view, double eps_lift, const gc_render_batch* out,
                                       int64_t* h_count);
 
-#define GC_BEV_CFG_LEN 11 /* [origin_x, origin_y, px_per_m, eps, opacity_gamma, logdet0, alpha_min, fbm_octaves,
-                             fbm_gain, fbm_seed, fbm_modulate_scale] (the viewport, SplatRenderingConfig
-                             rendering.py:28-44, and render_tile_ewa's fbm arguments :307-310) */
+/* The viewport, SplatRenderingConfig (rendering.py:28-44) and render_tile_ewa's fbm arguments (:307-310) */
+typedef struct {
+  double origin_x;
+  double origin_y;
+  double px_per_m;
+  double eps;
+  double opacity_gamma;
+  double logdet0;
+  double alpha_min;
+  double fbm_octaves;
+  double fbm_gain;
+  double fbm_seed;
+  double fbm_modulate_scale;
+} gc_bev_cfg;
 /* The 2D splats of n_views views of n primitives, view-major. The caller allocates every array. */
 typedef struct gc_bev_splats {
   double* means_px;   /* (n_views, n, 2) column, row */
@@ -1349,7 +1449,7 @@ typedef struct gc_bev_splats {
    [1, 32], n_lobes outside [1, 8], px_per_m <= 0, fbm_octaves not an integer in [0, 32], fbm_seed not
    an integer in [0, 2^31), a non-finite host value or NULL pointers. */
 int32_t gc_bev_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_P,
-                          const double* h_view_dirs, const double* h_cfg, const gc_bev_splats* out);
+                          const double* h_view_dirs, const gc_bev_cfg* cfg, const gc_bev_splats* out);
 
 /* splat_indices_for_tile (rendering.py:252-289) for every tile of every view, then render_tile_ewa
    (:297-355) over each tile's list. Tiles are row-major, T = (H / tile_size) (W / tile_size) per view;
@@ -1390,8 +1490,22 @@ int32_t gc_fbm_at_positions(gc_ctx* ctx, int64_t n, const double* d_xy, int32_t 
  * The camera view of the map: perspective splats, depth-ordered tile lists, front-to-back compositing
  * (tools/view_splat_jaxsplat.py around jaxsplat.render_v2; the raster itself is this build's).
  * ------------------------------------------------------------------------------------------ */
-#define GC_CAMVIEW_CFG_LEN 13 /* [near, far, lowpass_px2, radius_sigma, alpha_floor, alpha_max, alpha_skip, t_stop,
-                             background r, g, b, shade (0 or 1), eps] (CameraViewConfig) */
+/* CameraViewConfig */
+typedef struct {
+  double near; /* near and far are macros of some toolchains' system headers (windows.h): #undef them there */
+  double far;
+  double lowpass_px2;
+  double radius_sigma;
+  double alpha_floor;
+  double alpha_max;
+  double alpha_skip;
+  double t_stop;
+  double bg_r; /* the background colour */
+  double bg_g;
+  double bg_b;
+  double shade; /* 0 or 1 */
+  double eps;
+} gc_camview_cfg;
 /* The 2D splats of n_views camera views of n primitives, view-major. The caller allocates every array. */
 typedef struct gc_cam_splats {
   double* means_px;   /* (n_views, n, 2) column, row */
@@ -1419,7 +1533,7 @@ typedef struct gc_cam_splats {
    T_cw other than (0, 0, 0, 1), max |R^T R - I| > 1e-9, near <= 0, far <= near, alpha_max outside
    (0, 1] or NULL pointers. n = 0 launches nothing. */
 int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_views, const double* h_T_cw,
-                             const double* h_intrinsics, int32_t H, int32_t W, const double* h_cfg,
+                             const double* h_intrinsics, int32_t H, int32_t W, const gc_camview_cfg* cfg,
                              const gc_cam_splats* out);
 
 /* The tile lists and the composited images of camera splats. Tiles as in gc_render_ewa_tiles: tile
@@ -1438,9 +1552,9 @@ int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t 
    non-finite configuration value, near <= 0, far <= near, alpha_max outside (0, 1],
    n_views * T * n >= 2^32 or NULL pointers. */
 int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_cam_splats* splats, int32_t H, int32_t W,
-                              int32_t tile_size, int32_t cap, const double* h_cfg, double* d_images, double* d_alpha,
-                              double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts, int32_t* d_tile_survivors,
-                              int32_t* d_tile_indices);
+                              int32_t tile_size, int32_t cap, const gc_camview_cfg* cfg, double* d_images,
+                              double* d_alpha, double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts,
+                              int32_t* d_tile_survivors, int32_t* d_tile_indices);
 
 #ifdef __cplusplus
 }

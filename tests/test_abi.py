@@ -116,7 +116,52 @@ def test_binding_is_the_headers():
     assert "GC_PCERT_MF" not in consts and not hasattr(_abi, "GC_PCERT_MF")
     assert len(_abi.GC_STAGE_NAMES) == _abi.GC_STAGE_N and len(_abi.GC_HS_NAMES) <= _abi.GC_HOST_STATS
     assert _abi.PipelineDims._fields_ == structs["gc_pipeline_dims"]._fields_
-    assert len(structs) == 10
+    assert len(structs) == 10 + len(CFG_BUILDERS)
+
+
+def _cfg_builders():
+    from gcslam import association, pipeline, primitive_map, rendering
+    from gcslam.ops import camera_features, camera_splats, keypoint_detector, lidar_surfel_extraction
+    mu = primitive_map.MapUpdateConfig()
+    return dict(
+        gc_pipeline_cfg=lambda: pipeline.PipelineConfig().as_struct(4),
+        gc_map_update_cfg=lambda: _abi.cfg("gc_map_update_cfg", mu),
+        gc_map_maintain_cfg=lambda: _abi.cfg("gc_map_maintain_cfg", mu),
+        gc_ot_cfg=lambda: association._cfg(association.AssociationConfig(), 1e-9),
+        gc_surfel_cfg=lambda: _abi.cfg("gc_surfel_cfg", lidar_surfel_extraction.SurfelExtractionConfig(), n_lobes=3),
+        gc_cam_cfg=lambda: camera_splats._cfg(camera_splats.LidarCameraDepthFusionConfig()),
+        gc_camfeat_cfg=lambda: camera_features._cfg(camera_features.VisualFeatureConfig()),
+        gc_kp_cfg=lambda: keypoint_detector._cfg(keypoint_detector.OrbDetectorConfig()),
+        gc_bev_cfg=lambda: rendering._bev_cfg(rendering.Viewport((0.0, 0.0), 8.0, 32, 32), rendering.SplatRenderingConfig(),
+                                              0, 0.0),
+        gc_camview_cfg=lambda: rendering._camview_cfg(rendering.CameraViewConfig()))
+
+
+CFG_BUILDERS = _cfg_builders()
+
+
+@pytest.mark.parametrize("name", list(CFG_BUILDERS))
+def test_configuration_structs(name):
+    """Every gc_*_cfg of the header is doubles only and unpadded, _abi.cfg builds it from exactly its member
+    names, and the module that passes it fills every member from its default configuration."""
+    st = _abi.STRUCTS[name]
+    names = [n for n, _ in st._fields_]
+    assert names and all(t is ctypes.c_double for _, t in st._fields_)
+    assert ctypes.sizeof(st) == 8 * len(names)
+    values = {n: float(i) for i, n in enumerate(names)}
+    c = _abi.cfg(name, values)
+    assert isinstance(c, st) and [getattr(c, n) for n in names] == list(values.values())
+    with pytest.raises(TypeError, match=names[-1] + " is not given"):
+        _abi.cfg(name, {n: v for n, v in values.items() if n != names[-1]})
+    with pytest.raises(TypeError, match="no member no_such_member"):
+        _abi.cfg(name, dict(values, no_such_member=1.0))
+    built = CFG_BUILDERS[name]()
+    assert isinstance(built, st) and all(getattr(built, n) == getattr(built, n) for n in names)  # filled, no NaN
+
+
+def test_cfg_refuses_a_struct_that_is_not_all_double():
+    with pytest.raises(TypeError, match="H_total is not a double"):
+        _abi.cfg("gc_pipeline_dims", {n: 0 for n, _ in _abi.PipelineDims._fields_})
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libgcslam.so not built")

@@ -212,16 +212,19 @@ def test_select_keypoints():
 
 def test_config_is_the_nodes():
     cfg = VisualFeatureConfig()
-    h = CF._cfg_vector(cfg)
-    assert h.shape == (_abi.GC_CAMFEAT_CFG_LEN,) == (24,) and _abi.GC_CAMFEAT_AUX == 6 == len(CF.AUX_NAMES)
+    h = CF._cfg(cfg)
+    assert len(h._fields_) == 24 and _abi.GC_CAMFEAT_AUX == 6 == len(CF.AUX_NAMES)
     # visual_feature_node.cpp:74-101 / config/gc_unified.yaml:107-132
-    assert h.tolist() == [1.0, 1.0, 0.0, 0.01, 0.01, 0.05, 80.0, 5.0, 50.0, 1.0, 1e-9, 1e6, 2.0, 2.0, 6.0, 1e-8, 3.0,
-                          0.1, 10.0, 1e-4, 1.0, 10.0, 100.0, 0.1]
+    assert [getattr(h, name) for name, _ in h._fields_] == [
+        1.0, 1.0, 0.0, 0.01, 0.01, 0.05, 80.0, 5.0, 50.0, 1.0, 1e-9, 1e6, 2.0, 2.0, 6.0, 1e-8, 3.0, 0.1, 10.0, 1e-4, 1.0,
+        10.0, 100.0, 0.1]
     assert cfg.max_features == 512
-    assert CF._cfg_vector(VisualFeatureConfig(depth_sample_mode="hex", depth_model="quadratic"))[[0, 2]].tolist() == [3, 1]
+    h = CF._cfg(VisualFeatureConfig(depth_sample_mode="hex", depth_model="quadratic"))
+    assert [h.depth_sample_mode, h.depth_model] == [3, 1]
     with pytest.raises(Exception):
         cfg.kappa0 = 2.0  # frozen
-    assert CF._cfg_vector(VisualFeatureConfig(hex_radius=0, quad_fit_radius=-4))[[12, 13]].tolist() == [0.0, -4.0]
+    h = CF._cfg(VisualFeatureConfig(hex_radius=0, quad_fit_radius=-4))
+    assert [h.hex_radius, h.quad_fit_radius] == [0.0, -4.0]
 
 
 def _args(**kw):

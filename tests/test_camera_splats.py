@@ -218,7 +218,7 @@ def test_feature_list_packing(monkeypatch):
 
 def test_config_has_the_reference_fields():
     c = LidarCameraDepthFusionConfig()
-    assert len(CS._cfg_vector(c)) == _abi.GC_CAM_CFG_LEN == 23
+    assert len(CS._cfg(c)._fields_) == 23
     assert (c.lidar_projection_radius_pix, c.lidar_plane_fit_min_points, c.lidar_ray_plane_fit_max_points) == (3.0, 3, 64)
     assert (c.depth_min_m, c.depth_sigma_max_sq, c.depth_min_sigmoid_alpha_z, c.gamma_lidar) == (0.05, 1e4, 20.0, 1.0)
     with pytest.raises(Exception):

@@ -11,6 +11,8 @@ cond(AᵀA + εI) < 1e6 and |det H_uv| / ‖H_uv‖_F² >= 1e-4 (camfeat_restate
 finite on the others. The measured fractions of the bar are printed by test_gpu_camfeat_parity and
 recorded in DESIGN.md §4."""
 
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -20,6 +22,7 @@ from gcslam import _abi
 from gcslam.measurement_batch import BATCH_ARRAYS
 from gcslam.ops import (CameraFeatures, DeviceCameraFeatures, PinholeIntrinsics, SurfelExtractionConfig,
                         VisualFeatureConfig, camera_measurement_batch, extract_lidar_surfels, lift_camera_features)
+from gcslam.ops import camera_features as CF
 from gcslam.ops.camera_features import AUX_NAMES
 
 BAR = 1e-10
@@ -176,12 +179,13 @@ def test_gpu_camfeat_device_chain(ctx):
 def _raw_call(ctx, H=4, W=4, depth=1, M=0, intr=(10.0, 10.0, 2.0, 2.0), cfg=None):
     """gc_camera_features_lift itself with M = 0 (no buffer is touched): the entry's own argument checks."""
     h_k = np.array(intr, np.float64)
-    h_cfg = np.array(cfg if cfg is not None else
-                     [1, 1, 0, 0.01, 0.01, 0.05, 80, 5, 50, 1, 1e-9, 1e6, 2, 2, 6, 1e-8, 3, 0.1, 10, 1e-4, 1, 10, 100, 0.1],
-                     np.float64)
+    c_cfg = CF._cfg(VisualFeatureConfig())
+    for name, v in (cfg or {}).items():
+        getattr(c_cfg, name)  # a member of gc_camfeat_cfg
+        setattr(c_cfg, name, v)
     buf = _abi.DeviceArray(ctx, (16,), np.float32)
     _abi.call("gc_camera_features_lift", ctx.handle, H, W, buf.ptr if depth else None, None, M, None, h_k.ctypes.data,
-              h_cfg.ctypes.data, *([None] * 12), ctx=ctx)
+              ctypes.byref(c_cfg), *([None] * 12), ctx=ctx)
 
 
 @pytest.mark.gpu
@@ -224,18 +228,13 @@ def test_gpu_camfeat_edges(ctx):
         _lift(ctx, case, depth=np.broadcast_to(np.float32(1.0), (8192, 8193)), rgb=None)
     # the entry's own checks, before any launch
     _raw_call(ctx)
-    nan_cfg = [1, 1, 0, 0.01, 0.01, 0.05, 80, 5, 50, 1, 1e-9, 1e6, 2, 2, 6, 1e-8, 3, 0.1, 10, 1e-4, 1, float("nan"), 100, 0.1]
-    base = [1, 1, 0, 0.01, 0.01, 0.05, 80, 5, 50, 1, 1e-9, 1e6, 2, 2, 6, 1e-8, 3, 0.1, 10, 1e-4, 1, 10, 100, 0.1]
-    def with_(i, v):
-        c = list(base)
-        c[i] = v
-        return c
-    _raw_call(ctx, cfg=with_(12, 0))       # max(1, r) first
-    _raw_call(ctx, cfg=with_(13, -7))
+    _raw_call(ctx, cfg=dict(hex_radius=0))       # max(1, r) first
+    _raw_call(ctx, cfg=dict(quad_fit_radius=-7))
     _raw_call(ctx, H=8192, W=8192)
     for bad in (dict(M=-1), dict(M=4097), dict(H=0), dict(W=0), dict(H=8192, W=8193), dict(depth=0),
-                dict(cfg=with_(12, 4)), dict(cfg=with_(13, 4)), dict(cfg=with_(13, 2.5)), dict(cfg=with_(14, 0)),
-                dict(cfg=with_(0, 4)), dict(cfg=with_(0, 1.5)), dict(cfg=with_(2, 2)), dict(cfg=nan_cfg),
+                dict(cfg=dict(hex_radius=4)), dict(cfg=dict(quad_fit_radius=4)), dict(cfg=dict(quad_fit_radius=2.5)),
+                dict(cfg=dict(quad_fit_min_points=0)), dict(cfg=dict(depth_sample_mode=4)),
+                dict(cfg=dict(depth_sample_mode=1.5)), dict(cfg=dict(depth_model=2)), dict(cfg=dict(kappa_alpha=float("nan"))),
                 dict(intr=(0.0, 10.0, 2.0, 2.0)), dict(intr=(10.0, 0.0, 2.0, 2.0)),
                 dict(intr=(10.0, 10.0, float("inf"), 2.0)), dict(intr=(10.0, 10.0, 2.0, float("nan")))):
         with pytest.raises(ValueError):

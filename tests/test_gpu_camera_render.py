@@ -153,37 +153,39 @@ def test_gpu_camera_entry_argument_errors(ctx):
     zb = _abi.DeviceArray(ctx, (64,), np.uint8)
     batch = R._BatchStruct(3, 0, *([z.ptr] * 8))
     st = R._CamSplatStruct(z.ptr, z.ptr, z.ptr, z.ptr, z.ptr, z.ptr, zb.ptr)
-    cfg0 = R._cam_cfg_vector(R.CameraViewConfig())
+
+    def with_cfg(name, v):
+        h = R._camview_cfg(R.CameraViewConfig())
+        getattr(h, name)  # a member of gc_camview_cfg
+        setattr(h, name, v)
+        return h
+    cfg0 = R._camview_cfg(R.CameraViewConfig())
 
     def prep(n=1, nv=1, T=None, K=(60.0, 60.0, 32.0, 24.0), H=48, W=64, cfg=None, lobes=3):
         T = np.ascontiguousarray(np.tile(np.eye(4), (max(nv, 1), 1, 1)) if T is None else T, np.float64)
         K = np.ascontiguousarray(np.tile(np.asarray(K, np.float64), (max(nv, 1), 1)))
-        h = cfg0.copy() if cfg is None else np.asarray(cfg, np.float64)
+        h = cfg0 if cfg is None else cfg
         bs = R._BatchStruct(lobes, 0, *([z.ptr] * 8))
         _abi.call("gc_camera_splat_prep", ctx.handle, ctypes.byref(bs), n, nv, T.ctypes.data, K.ctypes.data, H, W,
-                  h.ctypes.data, ctypes.byref(st), ctx=ctx)
-
-    def with_cfg(i, v):
-        h = cfg0.copy()
-        h[i] = v
-        return h
+                  ctypes.byref(h), ctypes.byref(st), ctx=ctx)
     bottom, skew, nanT = np.eye(4), np.eye(4), np.eye(4)
     bottom[3, 2], skew[0, 1], nanT[0, 3] = 0.5, 1e-6, np.nan
     for kw in (dict(n=-1), dict(n=(1 << 24) + 1), dict(nv=0), dict(nv=33), dict(lobes=0), dict(lobes=9), dict(H=0),
                dict(W=16385), dict(K=(0.0, 60.0, 32.0, 24.0)), dict(K=(60.0, -2.0, 32.0, 24.0)),
                dict(K=(60.0, 60.0, np.nan, 24.0)), dict(T=bottom[None]), dict(T=skew[None]), dict(T=nanT[None]),
-               dict(cfg=with_cfg(0, 0.0)), dict(cfg=with_cfg(1, 0.1)), dict(cfg=with_cfg(5, 0.0)),
-               dict(cfg=with_cfg(5, 1.5)), dict(cfg=with_cfg(2, np.nan)), dict(cfg=with_cfg(7, np.inf))):
+               dict(cfg=with_cfg("near", 0.0)), dict(cfg=with_cfg("far", 0.1)), dict(cfg=with_cfg("alpha_max", 0.0)),
+               dict(cfg=with_cfg("alpha_max", 1.5)), dict(cfg=with_cfg("lowpass_px2", np.nan)),
+               dict(cfg=with_cfg("t_stop", np.inf))):
         with pytest.raises(ValueError):
             prep(**kw)
 
     def tiles(n=1, nv=1, H=32, W=32, ts=16, cap=4, cfg=None):
-        h = cfg0.copy() if cfg is None else cfg
-        _abi.call("gc_render_depth_tiles", ctx.handle, nv, n, ctypes.byref(st), H, W, ts, cap, h.ctypes.data, z.ptr, z.ptr,
+        h = cfg0 if cfg is None else cfg
+        _abi.call("gc_render_depth_tiles", ctx.handle, nv, n, ctypes.byref(st), H, W, ts, cap, ctypes.byref(h), z.ptr, z.ptr,
                   z.ptr, zi.ptr, zi.ptr, zi.ptr, zi.ptr, ctx=ctx)
     for kw in (dict(ts=0), dict(ts=33), dict(H=40), dict(W=24), dict(H=0), dict(cap=0), dict(cap=257), dict(n=-1),
-               dict(nv=0), dict(nv=33), dict(cfg=with_cfg(0, -1.0)), dict(cfg=with_cfg(5, 2.0)),
-               dict(cfg=with_cfg(6, np.nan)), dict(n=1 << 24, nv=32, H=16384, W=16384)):
+               dict(nv=0), dict(nv=33), dict(cfg=with_cfg("near", -1.0)), dict(cfg=with_cfg("alpha_max", 2.0)),
+               dict(cfg=with_cfg("alpha_skip", np.nan)), dict(n=1 << 24, nv=32, H=16384, W=16384)):
         with pytest.raises(ValueError):
             tiles(**kw)
     # the context is usable afterwards: n = 0 through the entry gives empty lists and the background
@@ -195,8 +197,8 @@ def test_gpu_camera_entry_argument_errors(ctx):
         a.upload(np.ones(a.shape))
     for a in (nc, cnt, sv, idx):
         a.upload(np.ones(a.shape, np.int32))
-    h = with_cfg(8, 0.5)
-    _abi.call("gc_render_depth_tiles", ctx.handle, 2, 0, None, 8, 16, 8, 4, h.ctypes.data, img.ptr, al.ptr, dp.ptr, nc.ptr,
+    h = with_cfg("bg_r", 0.5)
+    _abi.call("gc_render_depth_tiles", ctx.handle, 2, 0, None, 8, 16, 8, 4, ctypes.byref(h), img.ptr, al.ptr, dp.ptr, nc.ptr,
               cnt.ptr, sv.ptr, idx.ptr, ctx=ctx)
     want = np.zeros(img.shape)
     want[..., 0] = 0.5

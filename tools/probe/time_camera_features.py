@@ -18,6 +18,7 @@ of M single-wave workgroups and is bound by its latency, not by bytes.
 """
 
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -62,15 +63,15 @@ def _stats(ms):
 def time_lift(ctx, d_depth, d_rgb, kp, mode, iters, warmup):
     from gcslam import _abi
     from gcslam.ops import VisualFeatureConfig
-    from gcslam.ops.camera_features import _OUT, _cfg_vector
-    h_cfg = _cfg_vector(VisualFeatureConfig(depth_sample_mode=mode))
+    from gcslam.ops.camera_features import _OUT, _cfg
+    c_cfg = _cfg(VisualFeatureConfig(depth_sample_mode=mode))
     h_k = np.array([FX, FY, CX, CY])
     d_kp = _abi.DeviceArray.from_host(ctx, kp)
     out = _abi.alloc_many(ctx, [((M,) + shp, dt) for _, shp, dt in _OUT])
 
     def call():
         _abi.call("gc_camera_features_lift", ctx.handle, H, W, d_depth.ptr, d_rgb.ptr, M, d_kp.ptr, h_k.ctypes.data,
-                  h_cfg.ctypes.data, *[o.ptr for o in out], ctx=ctx)
+                  C.byref(c_cfg), *[o.ptr for o in out], ctx=ctx)
 
     e0, e1 = _abi.Event(ctx), _abi.Event(ctx)
     for _ in range(warmup):

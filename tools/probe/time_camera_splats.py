@@ -21,6 +21,7 @@ median of --iters calls.
 """
 
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -62,7 +63,7 @@ def time_device(n, iters, warmup):
     from gcslam.constants import GC_EPS_LIFT, GC_N_FEAT, GC_N_SURFEL, GC_VMF_N_LOBES
     from gcslam.measurement_batch import BATCH_ARRAYS
     from gcslam.ops import LidarCameraDepthFusionConfig
-    from gcslam.ops.camera_splats import _cfg_vector
+    from gcslam.ops.camera_splats import _cfg
     ctx = _abi.default_context()
     base, uv = scene(n)
     f = CC.features(uv)
@@ -75,13 +76,13 @@ def time_device(n, iters, warmup):
                                 for k, (shp, _, _) in BATCH_ARRAYS.items()] +
                           [((M, 3), np.float64), ((M, 3, 3), np.float64), ((M,), np.uint8), ((M, _abi.GC_CAM_EV), np.float64),
                            ((M,), np.int32)])
-    h_cfg = _cfg_vector(LidarCameraDepthFusionConfig())
+    c_cfg = _cfg(LidarCameraDepthFusionConfig())
     h_k = np.array([FX, FY, CX, CY])
     R, t = np.ascontiguousarray(CC.R_BASE_CAMERA), np.ascontiguousarray(CC.T_BASE_CAMERA)
 
     def call():
         _abi.call("gc_camera_measurement_batch", ctx.handle, n, dp.ptr, R.ctypes.data, t.ctypes.data, M,
-                  *[d.ptr for d in dev], h_k.ctypes.data, h_cfg.ctypes.data, 1.0, 0.5, GC_N_FEAT, GC_N_SURFEL, L,
+                  *[d.ptr for d in dev], h_k.ctypes.data, C.byref(c_cfg), 1.0, 0.5, GC_N_FEAT, GC_N_SURFEL, L,
                   GC_EPS_LIFT, *[b.ptr for b in blk], ctx=ctx)
 
     e0, e1 = _abi.Event(ctx), _abi.Event(ctx)

@@ -13,6 +13,7 @@ come from running this probe on its own under `rocprofv3 --kernel-trace --stats`
 """
 
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -55,9 +56,9 @@ def shape_counts(plan, channels=3):
 def time_detect(ctx, name, image, iters, warmup):
     from gcslam import _abi
     from gcslam.ops import OrbDetectorConfig
-    from gcslam.ops.keypoint_detector import _cfg_vector, keypoints_plan
+    from gcslam.ops.keypoint_detector import _cfg, keypoints_plan
     cfg = OrbDetectorConfig()
-    h_cfg = _cfg_vector(cfg)
+    c_cfg = _cfg(cfg)
     plan = keypoints_plan(H, W, cfg)
     d_img = _abi.DeviceArray.from_host(ctx, image, np.uint8)
     d_pyr = _abi.DeviceArray(ctx, (plan["pyramid_bytes"],), np.uint8)
@@ -66,7 +67,7 @@ def time_detect(ctx, name, image, iters, warmup):
                                                    ((_abi.GC_KP_COUNTS_LEN,), np.int32)])
 
     def call():
-        _abi.call("gc_keypoints_detect", ctx.handle, H, W, 3, d_img.ptr, h_cfg.ctypes.data, d_pyr.ptr, d_kp.ptr,
+        _abi.call("gc_keypoints_detect", ctx.handle, H, W, 3, d_img.ptr, C.byref(c_cfg), d_pyr.ptr, d_kp.ptr,
                   d_meta.ptr, d_counts.ptr, ctx=ctx)
 
     e0, e1 = _abi.Event(ctx), _abi.Event(ctx)

@@ -43,14 +43,11 @@ def time_extract(ctx, n, iters, warmup):
     blk = _abi.alloc_many(ctx, [((n_total,) + (shp if k != "etas" else (L, 3)), BATCH_ARRAYS[k][2])
                                 for k, (shp, _, _) in BATCH_ARRAYS.items()] + [((cfg.n_surfel,), np.int32)])
     blk[0]._base.zero()
-    h_cfg = np.array([cfg.n_surfel, cfg.n_feat, cfg.voxel_size_m, cfg.hex3d_num_cells_1, cfg.hex3d_num_cells_2,
-                      cfg.hex3d_num_cells_z, cfg.hex3d_max_occupants, cfg.min_points_per_voxel,
-                      cfg.sensor_noise_var_per_axis, cfg.wishart_nu, cfg.wishart_psi_scale, cfg.kappa_main_scale,
-                      cfg.kappa_min, cfg.kappa_max, cfg.eig_min, cfg.eps_lift, L], np.float64)
+    c_cfg = _abi.cfg("gc_surfel_cfg", cfg, n_lobes=L)
     nv = C.c_int32(0)
 
     def call():
-        _abi.call("gc_extract_lidar_surfels", ctx.handle, n, dp.ptr, dt.ptr, dw.ptr, h_cfg.ctypes.data,
+        _abi.call("gc_extract_lidar_surfels", ctx.handle, n, dp.ptr, dt.ptr, dw.ptr, C.byref(c_cfg),
                   *[b.ptr for b in blk[:len(names)]], blk[-1].ptr, C.byref(nv), ctx=ctx)
 
     e0, e1 = _abi.Event(ctx), _abi.Event(ctx)
