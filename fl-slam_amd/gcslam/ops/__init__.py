@@ -40,9 +40,12 @@ from .camera_splats import (CameraFeatures, CameraSplatDiagnostics, DeviceCamera
                             feature_list_to_camera_batch, lidar_depth_evidence, measurement_batch_from_camera_splats)
 from .camera_features import VisualFeatureConfig, lift_camera_features, select_keypoints
 from .keypoint_detector import DeviceKeypoints, Keypoints, OrbDetectorConfig, detect_keypoints
+from .depth_pose_evidence import (DepthEvidenceConfig, DepthPoseEvidenceResult, depth_pose_evidence,
+                                  depth_pose_evidence_batched)
 from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "DepthEvidenceConfig", "DepthPoseEvidenceResult", "depth_pose_evidence", "depth_pose_evidence_batched",
     "OrbDetectorConfig", "Keypoints", "DeviceKeypoints", "detect_keypoints",
     "VisualFeatureConfig", "lift_camera_features", "select_keypoints", "DeviceCameraFeatures",
     "CameraFeatures", "CameraSplatDiagnostics", "LidarCameraDepthFusionConfig", "PinholeIntrinsics",

@@ -27,6 +27,8 @@ import numpy as np
 from .certificates import CertBundle, InfluenceCert, SupportCert, aggregate_certificates
 from .constants import GC_CHART_ID
 from .map_branch import MapBranch, MapBranchFront
+from .ops.depth_pose_evidence import (MAX_POSES, DepthEvidenceConfig, depth_pose_evidence_batched,
+                                      result_from_parts)
 from .ops.deskew_constant_twist import deskew_constant_twist
 from .ops.lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
 from .ops.point_budget import point_budget_resample
@@ -67,7 +69,8 @@ class PrimitiveStepResult:
     lidar_cert: np.ndarray               # the GC_LIDAR_CERT row the back ran on
     z_t: np.ndarray                      # hypothesis 0's recomposed world pose, the update's pose
     xi_body: np.ndarray                  # hypothesis 0's deskew twist
-    certs: list                          # [deskew, surfel, recency inflate, assoc, visual]
+    certs: list                          # [deskew, surfel, recency inflate, assoc, visual(, depth)]
+    depth_parts: Optional[np.ndarray] = None  # with a depth frame: the (H, GC_DEPTHEV_PARTS) rows that were added
 
 
 class PrimitiveScanStep:
@@ -98,10 +101,22 @@ class PrimitiveScanStep:
         return batch, dsk_cert, surfel_cert
 
     def run(self, slot: int, scan: dict, scan_count: int, timestamp: float, measurement_batch=None,
-            batch_certs: Sequence[CertBundle] = ()) -> PrimitiveStepResult:
+            batch_certs: Sequence[CertBundle] = (), depth_frame: Optional[dict] = None) -> PrimitiveStepResult:
         """One scan. With measurement_batch the caller's batch is used (batch_certs: its deskew / surfel
-        certificates, if any); otherwise it is built from the scan deskewed with hypothesis 0's twist."""
+        certificates, if any); otherwise it is built from the scan deskewed with hypothesis 0's twist.
+
+        depth_frame (an RGB-D depth frame of this scan): a dict with `depth` (H, W; float32 metres, host or
+        device) and `intrinsics` (PinholeIntrinsics), and optionally `R_base_camera`, `t_base_camera`,
+        `view_cfg` (CameraViewConfig) and `cfg` (DepthEvidenceConfig). The depth pose evidence
+        (ops/depth_pose_evidence.py) of every hypothesis's linearisation pose against the map as it
+        stands after MapBranch.front is added on the device into the front's L_lidar / h_lidar, and
+        hypothesis 0's certificate joins the evidence certificates. At most 32 hypotheses."""
         pipe, br = self.pipeline, self.branch
+        if depth_frame is not None:
+            if pipe.Hl > MAX_POSES:
+                raise ValueError(f"{pipe.Hl} hypotheses with a depth frame; at most {MAX_POSES} are supported")
+            if "depth" not in depth_frame or "intrinsics" not in depth_frame:
+                raise ValueError("depth_frame needs `depth` and `intrinsics`")
         pipe.stage_scan(slot, scan)
         pipe.scan_front(slot, scan, scan_count)
         # the one small download before the map branch (the reference's own sync, pipeline.py:811):
@@ -115,11 +130,24 @@ class PrimitiveScanStep:
         front = br.front(measurement_batch, center, lin_d, int(scan_count), device_out=True)
         inflate_cert, assoc_cert = front.certs
         vcert = visual_cert(front.vpe_cert, br.config.eps_lift, br.chart_id)
-        row = lidar_cert_row(list(batch_certs) + [assoc_cert, vcert], [inflate_cert])
+        evidence_certs = list(batch_certs) + [assoc_cert, vcert]
+        depth_certs, depth_parts = [], None
+        if depth_frame is not None:
+            dcfg = depth_frame.get("cfg") or DepthEvidenceConfig()
+            _, _, parts, render = depth_pose_evidence_batched(
+                br.atlas_map, depth_frame["intrinsics"], lin_d, depth_frame["depth"], depth_frame.get("R_base_camera"),
+                depth_frame.get("t_base_camera"), depth_frame.get("view_cfg"), dcfg,
+                accumulate_into=(front.device["L_lidar"], front.device["h_lidar"]), device_out=True)
+            depth_parts = parts
+            _, dcert, _ = result_from_parts(None, None, parts[0], render["depth"].shape[1:], dcfg.eps_lift, br.chart_id)
+            depth_certs = [dcert]
+        row = lidar_cert_row(evidence_certs + depth_certs, [inflate_cert])
         pipe.set_lidar_evidence(front.device["L_lidar"], front.device["h_lidar"], row)
         pipe.scan_back()
         pipe.finish_scan()
         z_t = pipe.scan_map_pose()[0].copy()
         upd = br.update(front, z_t, float(timestamp))
         return PrimitiveStepResult(front=front, update=upd, combined=pipe.combined(), lidar_cert=row, z_t=z_t,
-                                   xi_body=xi0.copy(), certs=list(batch_certs) + [inflate_cert, assoc_cert, vcert])
+                                   xi_body=xi0.copy(),
+                                   certs=list(batch_certs) + [inflate_cert, assoc_cert, vcert] + depth_certs,
+                                   depth_parts=depth_parts)

@@ -1556,6 +1556,72 @@ int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_
                               double* d_alpha, double* d_depth, int32_t* d_n_contrib, int32_t* d_tile_counts,
                               int32_t* d_tile_survivors, int32_t* d_tile_indices);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth pose evidence from the camera view: the rendered depth against an observed depth image,
+ * linearised in the pose by forward-mode tangents carried through the compositing (this build's,
+ * DESIGN.md §4, "Depth pose evidence").
+ *
+ * The tangent convention is visual_pose_evidence.py's (r = map - (R m + t) with d/dt = -I, :89-99;
+ * R_delta = R_scatter R_pred^T, :234-238): a world-frame decoupled perturbation delta = [dt, dtheta] of
+ * the body pose, t_wb' = t_wb + dt, R_wb' = Exp(dtheta) R_wb, so that L and h add to
+ * gc_visual_pose_evidence's in the same coordinates. With T_cw = inv(T_wb T_bc), R = R_cw,
+ * p = R mu + t_cw and e_k the k-th unit vector: dp/ddt_k = -R e_k, dp/ddtheta_k = R [mu - t_wb]x e_k,
+ * dR_cw/ddtheta_k = -R [e_k]x, dR_cw/ddt = 0.
+ * ------------------------------------------------------------------------------------------ */
+#define GC_DEPTHEV_PARTS 46   /* per pose: L6 (36, row-major) | h6 (6) | cost | n_used | sum_cov | sum_w */
+#define GC_DEPTHEV_PARTIAL 31 /* per (pose, tile): the 21 upper entries of w J J^T by rows | w J r (6) | cost |
+                                 n_used | sum_cov | sum_w */
+
+/* The six pose tangents of gc_camera_splat_prep's outputs, per (pose, primitive): h_T_cw and
+   h_intrinsics as that entry takes them (the same arrays), h_t_wb (n_poses, 3) the body positions the
+   rotations turn about (host); splats the prep's outputs for these views. With dp = (dx, dy, dz):
+   d_dmeans_px (n_poses, n, 6, 2) = (fx (dx/z - x dz/z^2), fy (dy/z - y dz/z^2)); d_ddepths
+   (n_poses, n, 6) = dz; d_dSigmas_inv (n_poses, n, 6, 3), the entries 00, 01, 11 of
+   -Sigma_inv dSigma_px Sigma_inv with dSigma_px = sym(dM Sigma M^T + M Sigma dM^T), dM = dJ R + J dR,
+   dJ00 = -fx dz/z^2, dJ02 = -fx (dtx/z^2 - 2 tx dz/z^3), dtx = dx where the tangent is not clamped and
+   +-lim dz where it is (the y row likewise); the low-pass term has no derivative. Rows that are not
+   valid are zero. No wait. GC_ERR_ARG before any launch for n outside [0, 2^24], n_poses outside
+   [1, 32], H or W outside [1, 16384], fx or fy <= 0, a non-finite host value, a bottom row of T_cw
+   other than (0, 0, 0, 1), max |R^T R - I| > 1e-9 (extrinsics that are no rotation show here), an
+   invalid configuration or NULL pointers. n = 0 launches nothing. */
+int32_t gc_camera_splat_jvp(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_poses, const double* h_T_cw,
+                            const double* h_t_wb, const double* h_intrinsics, int32_t H, int32_t W,
+                            const gc_camview_cfg* cfg, const gc_cam_splats* splats, double* d_dmeans_px,
+                            double* d_ddepths, double* d_dSigmas_inv);
+
+/* Gaussian pose evidence of an observed depth image d_depth_obs (H, W; float32, metres, device; shared
+   by the poses) against the rendered depth, per pose, over the lists d_tile_counts / d_tile_indices and
+   beside the images d_alpha / d_depth that gc_render_depth_tiles made for the same arguments. One
+   workgroup per (pose, tile), one thread per pixel (tile_size <= 16); compositing in list order with
+   that entry's branches (raw = alpha exp(-max(q, 0) / 2), a = min(alpha_max, raw), skipped below
+   alpha_skip, stop once T < t_stop), the state (T, D, dT[6], dD[6]) in registers:
+   dq = -2 d^T Sigma_inv dmean + d^T dSigma_inv d; da = -a dq / 2, or 0 where raw > alpha_max or q < 0;
+   dD += dT a z + T da z + T a dz; dT <- dT (1 - a) - T da. Branches, lists and their order are constants
+   of the linearisation. With A = d_alpha and the rendered depth d_depth, a pixel is used where
+   depth_obs is finite, min_depth < depth_obs < max_depth (strict) and A > eps; there
+   J = (dD A + D dT) / A^2, r = depth - depth_obs, sigma = sigma0 + slope depth_obs (depth_model 0) or
+   sigma0 + slope depth_obs^2 (1), u = (nu + 1) / (nu + (r / sigma)^2) (use_robust 0: u = 1),
+   w = A u / sigma^2 (a constant of the linearisation). L6 = sum w J J^T, h6 = -sum w J r,
+   cost = sum w r^2, n_used, sum_cov = sum A, sum_w = sum w over the used pixels: per tile by a
+   fixed-order workgroup sum, over the tiles in tile order; no atomics, bitwise reproducible.
+   d_parts (n_poses, GC_DEPTHEV_PARTS). accumulate 0: d_L_pose (n_poses, 22, 22) = L6 + eps_lift I in
+   [0:6, 0:6] and zeros elsewhere, d_h_pose (n_poses, 22) = h6 in [0:6] and zeros; accumulate 1: L6 and h6
+   are added into the caller's d_L_pose and d_h_pose, no lift, nothing else touched. d_residual and
+   d_weight (n_poses, H, W; either may be NULL) receive r and w, zero where the pixel is not used.
+   No wait; uses the context's scratch. n = 0: no raster; the no-pixel outputs (L6 = 0, h6 = 0).
+   GC_ERR_ARG before any launch for n_poses outside [1, 32], tile_size outside [1, 16], H or W not a
+   multiple of tile_size in [1, 16384], cap outside [1, 256], n < 0, an invalid configuration,
+   depth_model not 0 or 1, sigma0 <= 0, slope < 0, min_depth >= max_depth or min_depth < 0, use_robust
+   with nu <= 0, a non-finite parameter, eps_lift < 0, n_poses * T * n >= 2^32 or NULL pointers. */
+int32_t gc_depth_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc_cam_splats* splats,
+                               const double* d_dmeans_px, const double* d_ddepths, const double* d_dSigmas_inv,
+                               int32_t H, int32_t W, int32_t tile_size, int32_t cap, const gc_camview_cfg* cfg,
+                               const int32_t* d_tile_counts, const int32_t* d_tile_indices, const double* d_alpha,
+                               const double* d_depth, const float* d_depth_obs, int32_t depth_model, double sigma0,
+                               double slope, double min_depth, double max_depth, int32_t use_robust, double robust_nu,
+                               double eps_lift, int32_t accumulate, double* d_L_pose, double* d_h_pose,
+                               double* d_parts, double* d_residual, double* d_weight);
+
 #ifdef __cplusplus
 }
 #endif
