@@ -2,14 +2,15 @@
 // (tools/view_splat_jaxsplat.py) does with the exported map and the last pose, with the raster it
 // leaves to jaxsplat.render_v2 defined by this build ("Camera view").
 //
-//   gc_camera_splat_prep   per (view, primitive): p = R mu + t, the pinhole mean, the perspective
-//                          pushforward M Sigma M^T with the Jacobian at clamped tangents, its closed-form
+//   gc_camera_splat_prep   per (view, primitive): cam_project (gc_renderdev.h: p = R mu + t, the pinhole
+//                          mean, M at clamped tangents), the pushforward M Sigma M^T, its closed-form
 //                          inverse and 3-sigma radius, the depth, the vMF shading towards the camera
 //                          centre; per primitive alpha = clip(mass / m_max, alpha_floor, 1)
 //                          (view_splat_jaxsplat.py:108-111), m_max reduced on the device.
 //   gc_render_depth_tiles  per (view, tile): the cap nearest survivors of the bbox test by
 //                          (depth, index) through the LDS selection the BEV lists use
-//                          (gc_renderdev.h), then front-to-back compositing: one workgroup per tile,
+//                          (gc_renderdev.h), then front-to-back compositing (its step: cam_step_alpha,
+//                          cam_step_through there, shared with the depth evidence): one workgroup per tile,
 //                          the tile's records staged in LDS, every lane reading the same record per step,
 //                          each pixel's transmittance, colour, depth and count in registers in list order.
 //
@@ -27,20 +28,7 @@
 namespace gc {
 namespace {
 
-constexpr int kCamView = 19;  // per view: R (9, row-major), t (3), fx fy cx cy, the camera centre -R^T t (3)
 constexpr int kCamRec = 12;   // a record: mean 2, Sigma^-1 4, alpha, rgb 3, depth, one pad (16-B aligned records)
-
-// The views travel by value as a kernel argument, kCamViewsPerLaunch at a time (2432 B: with the batch and
-// the configuration the argument block stays below 4 KB); more views take a second launch.
-constexpr int kCamViewsPerLaunch = 16;
-struct CamViews {
-  double v[kCamViewsPerLaunch * kCamView];
-};
-
-struct CamCfg {
-  double near, far, lowpass, radius_sigma, alpha_floor, alpha_max, alpha_skip, t_stop, bg[3], eps;
-  int shade;
-};
 
 // ------------------------------------------------------------------------------------------------
 // splat preparation
@@ -65,8 +53,7 @@ __global__ __launch_bounds__(kRdT) void k_cam_mass_max(int64_t n, const double* 
 
 // views v0 .. v0 + n_views - 1 (n_views <= kCamViewsPerLaunch), one lane per (view, primitive)
 __global__ __launch_bounds__(kRdT) void k_cam_prep(int64_t n, int v0, int n_views, gc_render_batch b, CamViews views,
-                                                   CamCfg c, double Wd, double Hd, const unsigned long long* mass_max,
-                                                   gc_cam_splats out) {
+                                                   CamCfg c, const unsigned long long* mass_max, gc_cam_splats out) {
   const int64_t gl = (int64_t)blockIdx.x * kRdT + threadIdx.x;
   if (gl >= n * n_views) return;
   const int vl = (int)(gl / n);
@@ -74,26 +61,19 @@ __global__ __launch_bounds__(kRdT) void k_cam_prep(int64_t n, int v0, int n_view
   const int v = v0 + vl;
   const int64_t g = (int64_t)v * n + i;
   const double* V = views.v + kCamView * vl;
-  double R[9], t[3], mu[3], S[9];
+  double mu[3], S[9];
 #pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    R[q] = V[q];
-    S[q] = b.Sigma_world[9 * i + q];
-  }
+  for (int q = 0; q < 9; ++q) S[q] = b.Sigma_world[9 * i + q];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    t[q] = V[9 + q];
-    mu[q] = b.mu_world[3 * i + q];
-  }
-  const double fx = V[12], fy = V[13], cx = V[14], cy = V[15];
+  for (int q = 0; q < 3; ++q) mu[q] = b.mu_world[3 * i + q];
   if (v == 0) {  // alpha is the primitive's, the same for every view
     const unsigned long long mw = *mass_max;
     const double m_max = mw ? __longlong_as_double((long long)mw) : 1.0;
     out.alphas[i] = fmin(fmax(b.mass[i] / m_max, c.alpha_floor), 1.0);
   }
-  double p[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) p[r] = R[3 * r] * mu[0] + R[3 * r + 1] * mu[1] + R[3 * r + 2] * mu[2] + t[r];
+  CamProj P;
+  cam_project(V, mu, S, P);
+  const double *p = P.p, *M = P.M, *MS = P.MS;
   bool ok = fabs(p[0]) < HUGE_VAL && fabs(p[1]) < HUGE_VAL && fabs(p[2]) < HUGE_VAL;
 #pragma unroll
   for (int q = 0; q < 9; ++q) ok = ok && fabs(S[q]) < HUGE_VAL;
@@ -109,21 +89,6 @@ __global__ __launch_bounds__(kRdT) void k_cam_prep(int64_t n, int v0, int n_view
     out.valid[g] = 0;
     return;
   }
-  const double x = p[0], y = p[1], z = p[2];
-  // the Jacobian of the projection at tangents clamped to 1.3 x the frame's half extent
-  const double limx = 1.3 * fmax(cx, Wd - cx) / fx, limy = 1.3 * fmax(cy, Hd - cy) / fy;
-  const double tx = fmin(fmax(x / z, -limx), limx) * z, ty = fmin(fmax(y / z, -limy), limy) * z;
-  const double J00 = fx / z, J02 = -fx * tx / (z * z), J11 = fy / z, J12 = -fy * ty / (z * z);
-  double M[6], MS[6];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    M[k] = J00 * R[k] + J02 * R[6 + k];
-    M[3 + k] = J11 * R[3 + k] + J12 * R[6 + k];
-  }
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) MS[3 * r + k] = M[3 * r] * S[k] + M[3 * r + 1] * S[3 + k] + M[3 * r + 2] * S[6 + k];
   double Sp[4];
 #pragma unroll
   for (int r = 0; r < 2; ++r)
@@ -131,17 +96,17 @@ __global__ __launch_bounds__(kRdT) void k_cam_prep(int64_t n, int v0, int n_view
     for (int k = 0; k < 2; ++k) Sp[2 * r + k] = MS[3 * r] * M[3 * k] + MS[3 * r + 1] * M[3 * k + 1] + MS[3 * r + 2] * M[3 * k + 2];
   const double a = Sp[0] + c.lowpass, d = Sp[3] + c.lowpass, bb = 0.5 * (Sp[1] + Sp[2]);
   const double det = a * d - bb * bb;
-  out.means_px[2 * g] = fx * x / z + cx;
-  out.means_px[2 * g + 1] = fy * y / z + cy;
+  out.means_px[2 * g] = P.px;
+  out.means_px[2 * g + 1] = P.py;
   out.Sigmas_inv[4 * g] = d / det;
   out.Sigmas_inv[4 * g + 1] = -bb / det;
   out.Sigmas_inv[4 * g + 2] = -bb / det;
   out.Sigmas_inv[4 * g + 3] = a / det;
-  out.depths[g] = z;
+  out.depths[g] = p[2];
   out.radii[g] = c.radius_sigma * sqrt(rd_eig_max2(a, bb, d));
   double s = 1.0;
   if (c.shade) {  // towards the camera centre
-    const double vd[3] = {V[16] - mu[0], V[17] - mu[1], V[18] - mu[2]};
+    const double vd[3] = {V[kCvCentre] - mu[0], V[kCvCentre + 1] - mu[1], V[kCvCentre + 2] - mu[2]};
     s = rd_vmf_shading(b.eta, i, b.n_lobes, vd);
   }
 #pragma unroll
@@ -169,15 +134,15 @@ __global__ __launch_bounds__(kRdT) void k_cam_bin_select(int64_t n, TileGrid G, 
                                                          const double* radii, const uint8_t* valid, int cap,
                                                          int32_t* counts, int32_t* survivors, int32_t* indices) {
   const int64_t seg = blockIdx.x;
-  const int64_t v = seg / G.T;
-  const int t = (int)(seg - v * G.T);
+  int ox, oy;
+  const int64_t v = rd_seg_tile(seg, G, ox, oy);
   CamKey key;
   key.means = means + 2 * v * n;
   key.depths = depths + v * n;
   key.radii = radii + v * n;
   key.valid = valid + v * n;
-  key.x0 = (double)(G.ox0 + (t % G.tiles_x) * G.ts);
-  key.y0 = (double)(G.oy0 + (t / G.tiles_x) * G.ts);
+  key.x0 = (double)ox;
+  key.y0 = (double)oy;
   key.x1 = key.x0 + (double)G.ts;
   key.y1 = key.y0 + (double)G.ts;
   rd_select_smallest<true>(n, seg, key, cap, counts, survivors, indices);
@@ -206,12 +171,10 @@ struct CamRasterArgs {
 __global__ __launch_bounds__(kRdT) void k_cam_raster(CamRasterArgs A) {
   __shared__ double rec[kRdMaxCap * kCamRec];
   const int64_t seg = blockIdx.x;
-  const int64_t v = seg / A.G.T;
-  const int t = (int)(seg - v * A.G.T);
   const int ts = A.G.ts;
-  const int ox = A.G.ox0 + (t % A.G.tiles_x) * ts, oy = A.G.oy0 + (t / A.G.tiles_x) * ts;
-  int m = A.counts[seg];
-  m = m < 0 ? 0 : (m > A.cap ? A.cap : m);  // A.cap <= kRdMaxCap (the entry checks it)
+  int ox, oy;
+  const int64_t v = rd_seg_tile(seg, A.G, ox, oy);
+  const int m = rd_clamp_count(A.counts[seg], A.cap);  // A.cap <= kRdMaxCap (the entry checks it)
   constexpr int kPix = kRdMaxTile * kRdMaxTile / kRdT;
   const int nk = (ts * ts + kRdT - 1) / kRdT;  // pixel slots in use (1 at tile_size 16): the rest are skipped
   double px[kPix], py[kPix], C[kPix][3], D[kPix], Tr[kPix];
@@ -229,8 +192,7 @@ __global__ __launch_bounds__(kRdT) void k_cam_raster(CamRasterArgs A) {
     live[k] = p < ts * ts;
   }
   if ((int)threadIdx.x < m) {
-    int64_t i = (int64_t)A.indices[seg * A.cap + threadIdx.x];
-    i = i < 0 ? 0 : (i >= A.n ? A.n - 1 : i);
+    const int64_t i = rd_list_index(A.indices[seg * A.cap + threadIdx.x], A.n);
     const int64_t r = v * A.n + i;
     double* o = rec + kCamRec * threadIdx.x;
     o[0] = A.means[2 * r];
@@ -256,8 +218,8 @@ __global__ __launch_bounds__(kRdT) void k_cam_raster(CamRasterArgs A) {
     for (int k = 0; k < kPix; ++k) {
       if (k >= nk) break;  // workgroup-uniform
       const double d0 = px[k] - mx, d1 = py[k] - my;
-      const double q = (d0 * s00 + d1 * s10) * d0 + (d0 * s01 + d1 * s11) * d1;
-      const double a = fmin(A.c.alpha_max, al * exp(-0.5 * fmax(q, 0.0)));
+      double raw, a;
+      cam_step_alpha(al, rd_quad(d0, d1, s00, s01, s10, s11), A.c.alpha_max, raw, a);
       if (live[k] && a >= A.c.alpha_skip) {
         const double w = Tr[k] * a;
         C[k][0] += w * c0;
@@ -265,8 +227,7 @@ __global__ __launch_bounds__(kRdT) void k_cam_raster(CamRasterArgs A) {
         C[k][2] += w * c2;
         D[k] += w * dep;
         cnt[k] += 1;
-        Tr[k] *= 1.0 - a;
-        if (Tr[k] < A.c.t_stop) live[k] = false;  // the splat that crossed the threshold is composited
+        if (cam_step_through(Tr[k], a, A.c.t_stop)) live[k] = false;
       }
     }
   }
@@ -289,27 +250,6 @@ __global__ __launch_bounds__(kRdT) void k_cam_raster(CamRasterArgs A) {
 // host side
 // ------------------------------------------------------------------------------------------------
 
-unsigned cam_blocks(int64_t threads) { return (unsigned)((threads + kRdT - 1) / kRdT); }
-
-bool cam_finite(double x) { return fabs(x) <= 1e300; }
-
-// the configuration, checked
-int cam_cfg(gc_ctx* ctx, const gc_camview_cfg* h, CamCfg* c) {
-  GC_CHECK_ARG(ctx, cfg_all<13>(h, cam_finite), "the configuration must be finite");
-  c->near = h->near; c->far = h->far; c->lowpass = h->lowpass_px2; c->radius_sigma = h->radius_sigma;
-  c->alpha_floor = h->alpha_floor; c->alpha_max = h->alpha_max; c->alpha_skip = h->alpha_skip; c->t_stop = h->t_stop;
-  c->bg[0] = h->bg_r; c->bg[1] = h->bg_g; c->bg[2] = h->bg_b; c->shade = h->shade != 0.0;
-  c->eps = h->eps;
-  GC_CHECK_ARG(ctx, c->near > 0.0 && c->far > c->near, "near must be > 0 and far > near");
-  GC_CHECK_ARG(ctx, c->alpha_max > 0.0 && c->alpha_max <= 1.0, "alpha_max must be in (0, 1]");
-  return GC_OK;
-}
-
-int cam_check_frame(gc_ctx* ctx, int32_t H, int32_t W) {
-  GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "H and W must be in [1, 16384]");
-  return GC_OK;
-}
-
 }  // namespace
 }  // namespace gc
 
@@ -326,30 +266,10 @@ int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t 
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
   GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
-  if (int rc = cam_check_frame(ctx, H, W)) return rc;
   CamCfg c;
   if (int rc = cam_cfg(ctx, cfg, &c)) return rc;
   double hv[kRdMaxViews * kCamView];
-  for (int v = 0; v < n_views; ++v) {
-    const double* T = h_T_cw + 16 * v;
-    const double* K = h_intrinsics + 4 * v;
-    for (int q = 0; q < 16; ++q) GC_CHECK_ARG(ctx, cam_finite(T[q]), "T_cw must be finite");
-    for (int q = 0; q < 4; ++q) GC_CHECK_ARG(ctx, cam_finite(K[q]), "the intrinsics must be finite");
-    GC_CHECK_ARG(ctx, K[0] > 0.0 && K[1] > 0.0, "fx and fy must be > 0");
-    GC_CHECK_ARG(ctx, T[12] == 0.0 && T[13] == 0.0 && T[14] == 0.0 && T[15] == 1.0, "the bottom row of T_cw must be (0, 0, 0, 1)");
-    double* V = hv + kCamView * v;
-    for (int r = 0; r < 3; ++r) {
-      for (int k = 0; k < 3; ++k) V[3 * r + k] = T[4 * r + k];
-      V[9 + r] = T[4 * r + 3];
-    }
-    for (int r = 0; r < 3; ++r)
-      for (int k = 0; k < 3; ++k) {
-        const double g = V[r] * V[k] + V[3 + r] * V[3 + k] + V[6 + r] * V[6 + k] - (r == k ? 1.0 : 0.0);  // R^T R - I
-        GC_CHECK_ARG(ctx, fabs(g) <= 1e-9, "the 3 x 3 block of T_cw must be a rotation");
-      }
-    for (int q = 0; q < 4; ++q) V[12 + q] = K[q];
-    for (int k = 0; k < 3; ++k) V[16 + k] = -(V[k] * V[9] + V[3 + k] * V[10] + V[6 + k] * V[11]);  // -R^T t
-  }
+  if (int rc = cam_pack_views(ctx, n_views, h_T_cw, h_intrinsics, nullptr, H, W, hv)) return rc;
   if (n == 0) return GC_OK;
   GC_CHECK_ARG(ctx, batch->mu_world && batch->Sigma_world && batch->eta && batch->mass && batch->color, "NULL batch field");
   GC_CHECK_ARG(ctx, out->means_px && out->Sigmas_inv && out->depths && out->radii && out->alphas && out->colors && out->valid,
@@ -358,18 +278,13 @@ int32_t gc_camera_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t 
   if (int rc = carve_scratch(ctx, [&](Carver& cv) { word = cv.take<unsigned long long>(1); })) return rc;
   hipStream_t st = ctx->stream;
   GC_HIP(ctx, hipMemsetAsync(word, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_cam_mass_max, dim3(cam_blocks(n) < kCamMaxBlocks ? cam_blocks(n) : kCamMaxBlocks), dim3(kRdT), 0, st, n,
+  hipLaunchKernelGGL(k_cam_mass_max, dim3(rd_blocks(n) < kCamMaxBlocks ? rd_blocks(n) : kCamMaxBlocks), dim3(kRdT), 0, st, n,
                      (const double*)batch->mass, word);
   GC_LAUNCH_CHECK(ctx);
-  for (int v0 = 0; v0 < n_views; v0 += kCamViewsPerLaunch) {
-    const int nv = n_views - v0 < kCamViewsPerLaunch ? n_views - v0 : kCamViewsPerLaunch;
-    CamViews views = {};
-    for (int q = 0; q < nv * kCamView; ++q) views.v[q] = hv[v0 * kCamView + q];
-    hipLaunchKernelGGL(k_cam_prep, dim3(cam_blocks(n * nv)), dim3(kRdT), 0, st, n, v0, nv, *batch, views, c, (double)W,
-                       (double)H, (const unsigned long long*)word, *out);
-    GC_LAUNCH_CHECK(ctx);
-  }
-  return GC_OK;
+  return cam_each_launch(ctx, n_views, hv, [&](int v0, int nv, const CamViews& views) {
+    hipLaunchKernelGGL(k_cam_prep, dim3(rd_blocks(n * nv)), dim3(kRdT), 0, st, n, v0, nv, *batch, views, c,
+                       (const unsigned long long*)word, *out);
+  });
 }
 
 int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_cam_splats* splats, int32_t H, int32_t W,
@@ -378,25 +293,17 @@ int32_t gc_render_depth_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_
                               int32_t* d_tile_survivors, int32_t* d_tile_indices) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kRdMaxTile, "tile_size must be in [1, 32]");
-  if (int rc = cam_check_frame(ctx, H, W)) return rc;
-  GC_CHECK_ARG(ctx, H % tile_size == 0 && W % tile_size == 0, "H and W must be multiples of tile_size");
-  GC_CHECK_ARG(ctx, cap >= 1 && cap <= kRdMaxCap, "cap must be in [1, 256]");
-  GC_CHECK_ARG(ctx, n >= 0, "n must be >= 0");
-  GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
-  GC_CHECK_ARG(ctx, cfg != nullptr, "NULL configuration");
+  TileGrid G;
+  int64_t segs;
+  if (int rc = rd_tile_grid(ctx, n_views, n, H, W, tile_size, kRdMaxTile, cap,
+                            {"n_views must be in [1, 32]", "tile_size must be in [1, 32]", "H and W must be in [1, 16384]",
+                             "H and W must be multiples of tile_size", "n_views * tiles * n must be below 2^32"},
+                            &G, &segs))
+    return rc;
   CamRasterArgs A;
   if (int rc = cam_cfg(ctx, cfg, &A.c)) return rc;
   GC_CHECK_ARG(ctx, d_images && d_alpha && d_depth && d_n_contrib && d_tile_counts && d_tile_survivors && d_tile_indices,
                "NULL output buffer");
-  TileGrid G;
-  G.tiles_x = W / tile_size;
-  G.T = G.tiles_x * (H / tile_size);
-  G.ts = tile_size;
-  G.oy0 = G.ox0 = 0;
-  const int64_t segs = (int64_t)n_views * G.T;
-  GC_CHECK_ARG(ctx, segs < ((int64_t)1 << 31) && (n == 0 || segs < ((int64_t)1 << 32) / n),
-               "n_views * tiles * n must be below 2^32");
   hipStream_t st = ctx->stream;
   if (n == 0) {  // empty lists from memsets; the raster over them writes the background
     GC_HIP(ctx, hipMemsetAsync(d_tile_counts, 0, sizeof(int32_t) * (size_t)segs, st));

@@ -4,9 +4,10 @@
 // six tangents of its (T, D) forward through the compositing loop.
 //
 //   gc_camera_splat_jvp     per (pose, primitive): the six tangents of gc_camera_splat_prep's pixel mean,
-//                           depth and inverse pixel covariance.
+//                           depth and inverse pixel covariance, from the same cam_project (gc_renderdev.h).
 //   gc_depth_pose_evidence  per (pose, tile): the tile's list staged through LDS in chunks of kEvChunk
-//                           records, one thread per pixel with (T, D, dT[6], dD[6]) in registers, then
+//                           records, one thread per pixel with (T, D, dT[6], dD[6]) in registers, stepped
+//                           by the camera raster's cam_step_alpha / cam_step_through (gc_renderdev.h), then
 //                           J, r, w per pixel and one fixed-order workgroup sum of the 31 values; per pose:
 //                           the tiles in tile order, and L_pose / h_pose / parts filled or accumulated.
 //
@@ -25,8 +26,6 @@ namespace gc {
 namespace {
 
 constexpr int kEvMaxTile = 16;  // a thread owns one pixel
-constexpr int kEvView = 22;     // per pose: R (9), t (3), fx fy cx cy, t_wb (3), limx, limy, one pad
-constexpr int kEvViewsPerLaunch = 16;
 constexpr int kEvRec = 44;      // a record: mean 2, Sigma^-1 4, alpha, depth, dmean 12, ddepth 6, dSigma^-1 18
 constexpr int kEvChunk = 64;    // records staged per barrier pair: 22 KB of LDS
 constexpr int kEvNV = GC_DEPTHEV_PARTIAL;
@@ -35,17 +34,13 @@ static_assert(kEvNV == 21 + 6 + 4 && kEvParts == 36 + 6 + 4, "gcslam.h");
 static_assert(kEvMaxTile * kEvMaxTile == kRdT, "one thread per pixel of the largest tile");
 static_assert(kRdT % 4 == 0 && kEvRec % 4 == 0 && kEvChunk * 4 == kRdT, "four threads stage one record");
 
-struct EvViews {
-  double v[kEvViewsPerLaunch * kEvView];
-};
-
 // ------------------------------------------------------------------------------------------------
 // tangent prep
 // ------------------------------------------------------------------------------------------------
 
-// poses v0 .. v0 + n_views - 1, one lane per (pose, primitive); the forward quantities are recomputed as
-// k_cam_prep computes them, the inverse pixel covariance and the validity are read from its outputs
-__global__ __launch_bounds__(kRdT) void k_ev_jvp(int64_t n, int v0, int n_views, gc_render_batch b, EvViews views,
+// poses v0 .. v0 + n_views - 1, one lane per (pose, primitive); the forward quantities are cam_project's, as
+// in k_cam_prep, the inverse pixel covariance and the validity are read from that kernel's outputs
+__global__ __launch_bounds__(kRdT) void k_ev_jvp(int64_t n, int v0, int n_views, gc_render_batch b, CamViews views,
                                                  const double* Sinv, const uint8_t* valid, double* dmeans,
                                                  double* ddepths, double* dSinv) {
   const int64_t gl = (int64_t)blockIdx.x * kRdT + threadIdx.x;
@@ -65,42 +60,35 @@ __global__ __launch_bounds__(kRdT) void k_ev_jvp(int64_t n, int v0, int n_views,
     for (int q = 0; q < 18; ++q) os[q] = 0.0;
     return;
   }
-  const double* V = views.v + kEvView * vl;
-  double R[9], S[9], mu[3], p[3], rel[3];
+  const double* V = views.v + kCamView * vl;
+  double R[9], S[9], mu[3], rel[3];
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
-    R[q] = V[q];
+    R[q] = V[kCvR + q];
     S[q] = b.Sigma_world[9 * i + q];
   }
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     mu[q] = b.mu_world[3 * i + q];
-    rel[q] = mu[q] - V[16 + q];
+    rel[q] = mu[q] - V[kCvTwb + q];
   }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) p[r] = R[3 * r] * mu[0] + R[3 * r + 1] * mu[1] + R[3 * r + 2] * mu[2] + V[9 + r];
-  const double fx = V[12], fy = V[13], limx = V[19], limy = V[20];
-  const double x = p[0], y = p[1], z = p[2];
-  const double ux = x / z, uy = y / z;
-  const double tx = fmin(fmax(ux, -limx), limx) * z, ty = fmin(fmax(uy, -limy), limy) * z;
+  CamProj P;
+  cam_project(V, mu, S, P);
+  const double *M = P.M, *MS = P.MS;
+  const double fx = V[kCvFx], fy = V[kCvFy], limx = V[kCvLimX], limy = V[kCvLimY];
+  const double x = P.p[0], y = P.p[1], z = P.p[2];
+  const double ux = P.ux, uy = P.uy, tx = P.tx, ty = P.ty;
   // dtx = cx_d dx + cx_z dz: (1, 0) where the tangent is free, (0, +-lim) where it is clamped
   const double cxd = (ux < -limx || ux > limx) ? 0.0 : 1.0, cxz = ux < -limx ? -limx : (ux > limx ? limx : 0.0);
   const double cyd = (uy < -limy || uy > limy) ? 0.0 : 1.0, cyz = uy < -limy ? -limy : (uy > limy ? limy : 0.0);
   const double iz = 1.0 / z, iz2 = iz * iz, iz3 = iz2 * iz;
-  const double J00 = fx / z, J02 = -fx * tx / (z * z), J11 = fy / z, J12 = -fy * ty / (z * z);
-  double M[6], MS[6], SMt[6];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    M[k] = J00 * R[k] + J02 * R[6 + k];
-    M[3 + k] = J11 * R[3 + k] + J12 * R[6 + k];
-  }
+  const double J00 = P.J00, J02 = P.J02, J11 = P.J11, J12 = P.J12;
+  double SMt[6];
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      MS[3 * r + k] = M[3 * r] * S[k] + M[3 * r + 1] * S[3 + k] + M[3 * r + 2] * S[6 + k];       // (M S)[r][k]
+    for (int k = 0; k < 3; ++k)
       SMt[3 * r + k] = S[3 * k] * M[3 * r] + S[3 * k + 1] * M[3 * r + 1] + S[3 * k + 2] * M[3 * r + 2];  // (S M^T)[k][r]
-    }
   const double i00 = Sinv[4 * g], i01 = Sinv[4 * g + 1], i11 = Sinv[4 * g + 3];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -161,6 +149,7 @@ __global__ __launch_bounds__(kRdT) void k_ev_jvp(int64_t n, int v0, int n_views,
 // the evidence raster
 // ------------------------------------------------------------------------------------------------
 
+// the part of the camera view's configuration the evidence reads (from a checked CamCfg), then its own
 struct EvCfg {
   double alpha_max, alpha_skip, t_stop, eps;
   double sigma0, slope, dmin, dmax, nu;
@@ -187,12 +176,10 @@ __global__ __launch_bounds__(kRdT) void k_ev_raster(EvRasterArgs A) {
   __shared__ double rec[kEvChunk * kEvRec];
   __shared__ double red[(kRdT / 64) * kEvNV];
   const int64_t seg = blockIdx.x;
-  const int64_t v = seg / A.G.T;
-  const int t = (int)(seg - v * A.G.T);
   const int ts = A.G.ts;
-  const int ox = (t % A.G.tiles_x) * ts, oy = (t / A.G.tiles_x) * ts;
-  int m = A.counts[seg];
-  m = m < 0 ? 0 : (m > A.cap ? A.cap : m);
+  int ox, oy;  // the image's: the grid's origin is 0 (rd_tile_grid)
+  const int64_t v = rd_seg_tile(seg, A.G, ox, oy);
+  const int m = rd_clamp_count(A.counts[seg], A.cap);
   const int p = threadIdx.x;
   const bool own = p < ts * ts;
   const int col = ox + (own ? p % ts : 0), row = oy + (own ? p / ts : 0);
@@ -207,8 +194,7 @@ __global__ __launch_bounds__(kRdT) void k_ev_raster(EvRasterArgs A) {
     {
       const int e = threadIdx.x >> 2, part = threadIdx.x & 3;
       if (e < mc) {
-        int64_t i = (int64_t)A.indices[seg * A.cap + c0 + e];
-        i = i < 0 ? 0 : (i >= A.n ? A.n - 1 : i);
+        const int64_t i = rd_list_index(A.indices[seg * A.cap + c0 + e], A.n);
         const int64_t r = v * A.n + i;
         double* o = rec + kEvRec * e;
         if (part == 0) {
@@ -238,9 +224,9 @@ __global__ __launch_bounds__(kRdT) void k_ev_raster(EvRasterArgs A) {
       const double* o = rec + kEvRec * j;
       const double mx = o[0], my = o[1], s00 = o[2], s01 = o[3], s10 = o[4], s11 = o[5], al = o[6], dep = o[7];
       const double d0 = px - mx, d1 = py - my;
-      const double q = (d0 * s00 + d1 * s10) * d0 + (d0 * s01 + d1 * s11) * d1;
-      const double raw = al * exp(-0.5 * fmax(q, 0.0));
-      const double a = fmin(A.c.alpha_max, raw);
+      const double q = rd_quad(d0, d1, s00, s01, s10, s11);
+      double raw, a;
+      cam_step_alpha(al, q, A.c.alpha_max, raw, a);
       if (live && a >= A.c.alpha_skip) {
         const bool flat = raw > A.c.alpha_max || q < 0.0;
         const double g0 = s00 * d0 + s01 * d1, g1 = s10 * d0 + s11 * d1;
@@ -255,8 +241,7 @@ __global__ __launch_bounds__(kRdT) void k_ev_raster(EvRasterArgs A) {
           dT[k] = dT[k] * na - Tr * da;
         }
         D += Ta * dep;
-        Tr *= na;
-        if (Tr < A.c.t_stop) live = false;
+        if (cam_step_through(Tr, a, A.c.t_stop)) live = false;
       }
     }
   }
@@ -344,19 +329,6 @@ __global__ __launch_bounds__(kRdT) void k_ev_final(int G, const double* partial,
 // host side
 // ------------------------------------------------------------------------------------------------
 
-unsigned ev_blocks(int64_t threads) { return (unsigned)((threads + kRdT - 1) / kRdT); }
-
-bool ev_finite(double x) { return fabs(x) <= 1e300; }
-
-// the part of the camera view's configuration the evidence reads, checked as gc_render_depth_tiles checks it
-int ev_cfg(gc_ctx* ctx, const gc_camview_cfg* h, EvCfg* c) {
-  GC_CHECK_ARG(ctx, cfg_all<13>(h, ev_finite), "the configuration must be finite");
-  GC_CHECK_ARG(ctx, h->near > 0.0 && h->far > h->near, "near must be > 0 and far > near");
-  GC_CHECK_ARG(ctx, h->alpha_max > 0.0 && h->alpha_max <= 1.0, "alpha_max must be in (0, 1]");
-  c->alpha_max = h->alpha_max; c->alpha_skip = h->alpha_skip; c->t_stop = h->t_stop; c->eps = h->eps;
-  return GC_OK;
-}
-
 }  // namespace
 }  // namespace gc
 
@@ -373,49 +345,20 @@ int32_t gc_camera_splat_jvp(gc_ctx* ctx, const gc_render_batch* batch, int64_t n
   GC_CHECK_ARG(ctx, batch && h_T_cw && h_t_wb && h_intrinsics && cfg && splats, "NULL argument");
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_poses >= 1 && n_poses <= kRdMaxViews, "n_poses must be in [1, 32]");
-  GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "H and W must be in [1, 16384]");
-  EvCfg c;
-  if (int rc = ev_cfg(ctx, cfg, &c)) return rc;
-  double hv[kRdMaxViews * kEvView];
-  for (int v = 0; v < n_poses; ++v) {
-    const double* T = h_T_cw + 16 * v;
-    const double* K = h_intrinsics + 4 * v;
-    for (int q = 0; q < 16; ++q) GC_CHECK_ARG(ctx, ev_finite(T[q]), "T_cw must be finite");
-    for (int q = 0; q < 4; ++q) GC_CHECK_ARG(ctx, ev_finite(K[q]), "the intrinsics must be finite");
-    for (int q = 0; q < 3; ++q) GC_CHECK_ARG(ctx, ev_finite(h_t_wb[3 * v + q]), "t_wb must be finite");
-    GC_CHECK_ARG(ctx, K[0] > 0.0 && K[1] > 0.0, "fx and fy must be > 0");
-    GC_CHECK_ARG(ctx, T[12] == 0.0 && T[13] == 0.0 && T[14] == 0.0 && T[15] == 1.0, "the bottom row of T_cw must be (0, 0, 0, 1)");
-    double* V = hv + kEvView * v;
-    for (int r = 0; r < 3; ++r) {
-      for (int k = 0; k < 3; ++k) V[3 * r + k] = T[4 * r + k];
-      V[9 + r] = T[4 * r + 3];
-    }
-    for (int r = 0; r < 3; ++r)
-      for (int k = 0; k < 3; ++k) {
-        const double g = V[r] * V[k] + V[3 + r] * V[3 + k] + V[6 + r] * V[6 + k] - (r == k ? 1.0 : 0.0);  // R^T R - I
-        GC_CHECK_ARG(ctx, fabs(g) <= 1e-9, "the 3 x 3 block of T_cw must be a rotation");
-      }
-    for (int q = 0; q < 4; ++q) V[12 + q] = K[q];
-    for (int q = 0; q < 3; ++q) V[16 + q] = h_t_wb[3 * v + q];
-    V[19] = 1.3 * fmax(K[2], (double)W - K[2]) / K[0];  // k_cam_prep's limx, limy
-    V[20] = 1.3 * fmax(K[3], (double)H - K[3]) / K[1];
-    V[21] = 0.0;
-  }
+  CamCfg c;
+  if (int rc = cam_cfg(ctx, cfg, &c)) return rc;
+  double hv[kRdMaxViews * kCamView];
+  if (int rc = cam_pack_views(ctx, n_poses, h_T_cw, h_intrinsics, h_t_wb, H, W, hv)) return rc;
   if (n == 0) return GC_OK;
   GC_CHECK_ARG(ctx, batch->mu_world && batch->Sigma_world, "NULL batch field");
   GC_CHECK_ARG(ctx, splats->Sigmas_inv && splats->valid, "NULL splat field");
   GC_CHECK_ARG(ctx, d_dmeans_px && d_ddepths && d_dSigmas_inv, "NULL output buffer");
   hipStream_t st = ctx->stream;
-  for (int v0 = 0; v0 < n_poses; v0 += kEvViewsPerLaunch) {
-    const int nv = n_poses - v0 < kEvViewsPerLaunch ? n_poses - v0 : kEvViewsPerLaunch;
-    EvViews views = {};
-    for (int q = 0; q < nv * kEvView; ++q) views.v[q] = hv[v0 * kEvView + q];
-    hipLaunchKernelGGL(k_ev_jvp, dim3(ev_blocks(n * nv)), dim3(kRdT), 0, st, n, v0, nv, *batch, views,
+  return cam_each_launch(ctx, n_poses, hv, [&](int v0, int nv, const CamViews& views) {
+    hipLaunchKernelGGL(k_ev_jvp, dim3(rd_blocks(n * nv)), dim3(kRdT), 0, st, n, v0, nv, *batch, views,
                        (const double*)splats->Sigmas_inv, (const uint8_t*)splats->valid, d_dmeans_px, d_ddepths,
                        d_dSigmas_inv);
-    GC_LAUNCH_CHECK(ctx);
-  }
-  return GC_OK;
+  });
 }
 
 int32_t gc_depth_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc_cam_splats* splats,
@@ -428,32 +371,27 @@ int32_t gc_depth_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc
                                double* d_parts, double* d_residual, double* d_weight) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  GC_CHECK_ARG(ctx, n_poses >= 1 && n_poses <= kRdMaxViews, "n_poses must be in [1, 32]");
-  GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kEvMaxTile, "tile_size must be in [1, 16]: a thread owns one pixel");
-  GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "H and W must be in [1, 16384]");
-  GC_CHECK_ARG(ctx, H % tile_size == 0 && W % tile_size == 0, "H and W must be multiples of tile_size");
-  GC_CHECK_ARG(ctx, cap >= 1 && cap <= kRdMaxCap, "cap must be in [1, 256]");
-  GC_CHECK_ARG(ctx, n >= 0, "n must be >= 0");
-  GC_CHECK_ARG(ctx, cfg != nullptr, "NULL configuration");
+  TileGrid G;
+  int64_t segs;
+  if (int rc = rd_tile_grid(ctx, n_poses, n, H, W, tile_size, kEvMaxTile, cap,
+                            {"n_poses must be in [1, 32]", "tile_size must be in [1, 16]: a thread owns one pixel",
+                             "H and W must be in [1, 16384]", "H and W must be multiples of tile_size",
+                             "n_poses * tiles * n must be below 2^32"},
+                            &G, &segs))
+    return rc;
+  CamCfg vc;
+  if (int rc = cam_cfg(ctx, cfg, &vc)) return rc;
   EvRasterArgs A;
-  if (int rc = ev_cfg(ctx, cfg, &A.c)) return rc;
+  A.c.alpha_max = vc.alpha_max; A.c.alpha_skip = vc.alpha_skip; A.c.t_stop = vc.t_stop; A.c.eps = vc.eps;
   GC_CHECK_ARG(ctx, depth_model == 0 || depth_model == 1, "depth_model must be 0 (linear) or 1 (quadratic)");
-  GC_CHECK_ARG(ctx, ev_finite(sigma0) && ev_finite(slope) && ev_finite(min_depth) && ev_finite(max_depth) &&
-                        ev_finite(eps_lift) && (!use_robust || ev_finite(robust_nu)),
+  GC_CHECK_ARG(ctx, rd_finite(sigma0) && rd_finite(slope) && rd_finite(min_depth) && rd_finite(max_depth) &&
+                        rd_finite(eps_lift) && (!use_robust || rd_finite(robust_nu)),
                "the evidence parameters must be finite");
   GC_CHECK_ARG(ctx, sigma0 > 0.0 && slope >= 0.0, "depth_sigma0 must be > 0 and depth_sigma_slope >= 0");
   GC_CHECK_ARG(ctx, min_depth >= 0.0 && max_depth > min_depth, "the depth limits must satisfy 0 <= min < max");
   GC_CHECK_ARG(ctx, !use_robust || robust_nu > 0.0, "robust_nu must be > 0");
   GC_CHECK_ARG(ctx, eps_lift >= 0.0, "eps_lift must be >= 0");
   GC_CHECK_ARG(ctx, d_L_pose && d_h_pose && d_parts, "NULL output buffer");
-  TileGrid G;
-  G.tiles_x = W / tile_size;
-  G.T = G.tiles_x * (H / tile_size);
-  G.ts = tile_size;
-  G.oy0 = G.ox0 = 0;
-  const int64_t segs = (int64_t)n_poses * G.T;
-  GC_CHECK_ARG(ctx, segs < ((int64_t)1 << 31) && (n == 0 || segs < ((int64_t)1 << 32) / n),
-               "n_poses * tiles * n must be below 2^32");
   hipStream_t st = ctx->stream;
   const size_t px = (size_t)n_poses * H * W;
   if (n == 0) {  // no raster over an empty range: the sums over no tile

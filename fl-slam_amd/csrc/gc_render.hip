@@ -242,9 +242,9 @@ __global__ __launch_bounds__(kRdT) void k_bev_prep(int64_t n, int n_views, gc_re
 // the four-sided bbox test rejects it (:283, the reference's strict inequalities).
 GC_DEV double rd_bin_key(int64_t n, int64_t seg, const TileGrid& G, const double* means, const double* Sinv,
                          double eps, int64_t i) {
-  const int64_t v = seg / G.T;
-  const int t = (int)(seg - v * G.T);
-  const double ox = (double)(G.ox0 + (t % G.tiles_x) * G.ts), oy = (double)(G.oy0 + (t / G.tiles_x) * G.ts);
+  int oxi, oyi;
+  const int64_t v = rd_seg_tile(seg, G, oxi, oyi);
+  const double ox = (double)oxi, oy = (double)oyi;
   const double* Si = Sinv + 4 * (v * n + i);
   // the smaller eigenvalue of the symmetric 2 x 2 (eigvalsh reads the lower triangle)
   const double lam = fmax(rd_eig_min2(Si[0], Si[2], Si[3]), eps);
@@ -322,10 +322,9 @@ struct RasterArgs {
 __global__ __launch_bounds__(kRdT) void k_raster(RasterArgs A) {
   __shared__ double rec[kRdMaxCap * kRdRec];
   const int64_t seg = blockIdx.x;
-  const int64_t v = seg / A.G.T;
-  const int t = (int)(seg - v * A.G.T);
   const int ts = A.G.ts;
-  const int ox = A.G.ox0 + (t % A.G.tiles_x) * ts, oy = A.G.oy0 + (t / A.G.tiles_x) * ts;
+  int ox, oy;
+  const int64_t v = rd_seg_tile(seg, A.G, ox, oy);
   const int64_t count = A.counts ? (int64_t)A.counts[seg] : A.n_list;
   constexpr int kPix = kRdMaxTile * kRdMaxTile / kRdT;
   double px[kPix], py[kPix], acc[kPix][3], wsum[kPix];
@@ -341,8 +340,7 @@ __global__ __launch_bounds__(kRdT) void k_raster(RasterArgs A) {
     const int m = (int)((count - base) < kRdMaxCap ? (count - base) : kRdMaxCap);
     __syncthreads();
     if ((int)threadIdx.x < m) {
-      int64_t i = A.indices ? (int64_t)A.indices[seg * A.stride + base + threadIdx.x] : base + threadIdx.x;
-      i = i < 0 ? 0 : (i >= A.n ? A.n - 1 : i);
+      const int64_t i = rd_list_index(A.indices ? (int64_t)A.indices[seg * A.stride + base + threadIdx.x] : base + threadIdx.x, A.n);
       const int64_t r = v * A.n + i;
       double* o = rec + kRdRec * threadIdx.x;
       o[0] = A.means[2 * r];
@@ -361,8 +359,7 @@ __global__ __launch_bounds__(kRdT) void k_raster(RasterArgs A) {
 #pragma unroll
       for (int k = 0; k < kPix; ++k) {
         const double d0 = px[k] - mx, d1 = py[k] - my;
-        // (d @ Sigma_inv) @ d, :85
-        const double q = (d0 * s00 + d1 * s10) * d0 + (d0 * s01 + d1 * s11) * d1;
+        const double q = rd_quad(d0, d1, s00, s01, s10, s11);
         const double arg = fmin(fmax(-0.5 * fmax(q, 0.0), -A.log_clip), 0.0);
         const double w = al * exp(arg);
         acc[k][0] += w * c0;
@@ -391,13 +388,6 @@ __global__ __launch_bounds__(kRdT) void k_raster(RasterArgs A) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-
-unsigned rd_blocks(int64_t threads) { return (unsigned)((threads + kRdT - 1) / kRdT); }
-
-int rd_check_tile(gc_ctx* ctx, int32_t tile_size) {
-  GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kRdMaxTile, "tile_size must be in [1, 32]");
-  return GC_OK;
-}
 
 // splat_indices_for_tile for the segments of G (n_views * G.T of them, n splats each): counts (one per
 // segment) and indices (cap per segment, -1 padded). n > 0, cap <= kRdMaxCap.
@@ -529,9 +519,9 @@ int32_t gc_bev_splat_prep(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, 
   GC_CHECK_ARG(ctx, n >= 0 && n <= ((int64_t)1 << 24), "n must be in [0, 2^24]");
   GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
   GC_CHECK_ARG(ctx, batch->n_lobes >= 1 && batch->n_lobes <= kMapMaxLobes, "n_lobes must be in [1, 8]");
-  GC_CHECK_ARG(ctx, cfg_all<11>(cfg, [](double v) { return fabs(v) <= 1e300; }), "the configuration must be finite");
-  for (int q = 0; q < 6 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_P[q]) <= 1e300, "P must be finite");
-  for (int q = 0; q < 3 * n_views; ++q) GC_CHECK_ARG(ctx, fabs(h_view_dirs[q]) <= 1e300, "view_dirs must be finite");
+  GC_CHECK_ARG(ctx, cfg_all<11>(cfg, rd_finite), "the configuration must be finite");
+  for (int q = 0; q < 6 * n_views; ++q) GC_CHECK_ARG(ctx, rd_finite(h_P[q]), "P must be finite");
+  for (int q = 0; q < 3 * n_views; ++q) GC_CHECK_ARG(ctx, rd_finite(h_view_dirs[q]), "view_dirs must be finite");
   BevCfg c;
   c.ox = cfg->origin_x; c.oy = cfg->origin_y; c.ppm = cfg->px_per_m; c.eps = cfg->eps; c.gamma = cfg->opacity_gamma;
   c.logdet0 = cfg->logdet0; c.alpha_min = cfg->alpha_min; c.octaves = (int)cfg->fbm_octaves; c.gain = cfg->fbm_gain;
@@ -560,22 +550,16 @@ int32_t gc_render_ewa_tiles(gc_ctx* ctx, int32_t n_views, int64_t n, const gc_be
                             int32_t* d_tile_counts, int32_t* d_tile_indices) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  if (int rc = rd_check_tile(ctx, tile_size)) return rc;
-  GC_CHECK_ARG(ctx, H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && H % tile_size == 0 && W % tile_size == 0,
-               "H and W must be multiples of tile_size in [1, 16384]");
-  GC_CHECK_ARG(ctx, cap >= 1 && cap <= kRdMaxCap, "cap must be in [1, 256]");
-  GC_CHECK_ARG(ctx, n >= 0, "n must be >= 0");
-  GC_CHECK_ARG(ctx, n_views >= 1 && n_views <= kRdMaxViews, "n_views must be in [1, 32]");
+  TileGrid G;
+  int64_t segs;
+  if (int rc = rd_tile_grid(ctx, n_views, n, H, W, tile_size, kRdMaxTile, cap,
+                            {"n_views must be in [1, 32]", "tile_size must be in [1, 32]",
+                             "H and W must be multiples of tile_size in [1, 16384]",
+                             "H and W must be multiples of tile_size in [1, 16384]", "n_views * tiles * n must be below 2^32"},
+                            &G, &segs))
+    return rc;
   GC_CHECK_ARG(ctx, log_clip == log_clip && eps == eps, "NaN scalar argument");
   GC_CHECK_ARG(ctx, d_images && d_tile_counts && d_tile_indices, "NULL output buffer");
-  TileGrid G;
-  G.tiles_x = W / tile_size;
-  G.T = G.tiles_x * (H / tile_size);
-  G.ts = tile_size;
-  G.oy0 = G.ox0 = 0;
-  const int64_t segs = (int64_t)n_views * G.T;
-  GC_CHECK_ARG(ctx, segs < ((int64_t)1 << 31) && (n == 0 || segs < ((int64_t)1 << 32) / n),
-               "n_views * tiles * n must be below 2^32");
   hipStream_t st = ctx->stream;
   if (n == 0) {
     GC_HIP(ctx, hipMemsetAsync(d_images, 0, sizeof(double) * 3 * (size_t)n_views * H * W, st));
@@ -602,7 +586,7 @@ int32_t gc_splat_indices_for_tile(gc_ctx* ctx, int64_t n, const double* d_means,
                                   int32_t* d_indices, int32_t* h_count) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  if (int rc = rd_check_tile(ctx, tile_size)) return rc;
+  GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kRdMaxTile, "tile_size must be in [1, 32]");
   GC_CHECK_ARG(ctx, n >= 0 && n < ((int64_t)1 << 31), "n must be in [0, 2^31)");
   GC_CHECK_ARG(ctx, cap >= 1 && cap <= (1 << 24), "cap must be in [1, 2^24]");
   GC_CHECK_ARG(ctx, abs(origin_y) <= (1 << 24) && abs(origin_x) <= (1 << 24), "tile origin outside [-2^24, 2^24]");
@@ -633,7 +617,7 @@ int32_t gc_render_tile_ewa(gc_ctx* ctx, int64_t n, const double* d_means, const 
                            double* d_image) {
   GC_CHECK_ARG(nullptr, ctx != nullptr, "ctx is NULL");
   if (int rc_j = join_side(ctx)) return rc_j;
-  if (int rc = rd_check_tile(ctx, tile_size)) return rc;
+  GC_CHECK_ARG(ctx, tile_size >= 1 && tile_size <= kRdMaxTile, "tile_size must be in [1, 32]");
   GC_CHECK_ARG(ctx, n >= 0 && n < ((int64_t)1 << 31), "n must be in [0, 2^31)");
   GC_CHECK_ARG(ctx, n_idx >= -1 && n_idx < ((int64_t)1 << 31), "n_idx must be -1 (every splat) or in [0, 2^31)");
   GC_CHECK_ARG(ctx, n_idx <= 0 || d_indices, "NULL index buffer");

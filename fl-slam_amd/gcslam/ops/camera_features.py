@@ -119,6 +119,20 @@ def _image_shape(x, what: str, channels: Optional[int]):
     return sh
 
 
+def _depth_image(depth, what: str):
+    """(H, W, image) of a depth image called `what`: the float32 DeviceArray itself, or the host image as
+    contiguous float32 (another float or integer dtype is converted)."""
+    H, W = _image_shape(depth, what, None)
+    if isinstance(depth, _abi.DeviceArray):
+        if depth.dtype != np.float32:
+            raise ValueError(f"device {what} of dtype {depth.dtype}, expected float32")
+        return H, W, depth
+    depth = np.asarray(depth)
+    if depth.dtype.kind not in "fiu":
+        raise ValueError(f"{what} of dtype {depth.dtype}, expected a float or integer image")
+    return H, W, np.ascontiguousarray(depth, dtype=np.float32)
+
+
 def _empty(m: int = 0) -> CameraFeatures:
     z = lambda *s: np.zeros((m,) + s, np.float64)
     return CameraFeatures(u=z(), v=z(), depth_Lambda_c=z(), depth_theta_c=z(), weight=z(), kappa_app=z(), mu_app=z(3),
@@ -159,17 +173,9 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
     except (TypeError, ValueError):
         raise ValueError("intrinsics must be a PinholeIntrinsics or [fx, fy, cx, cy]") from None
     h_k = _intr_vector(fx, fy, cx, cy)
-    H, W = _image_shape(depth, "depth", None)
+    H, W, depth = _depth_image(depth, "depth")
     if H < 1 or W < 1 or H * W > MAX_PIXELS:
         raise ValueError(f"a depth image of {H} x {W}; H and W must be >= 1 and H W <= 2^26")
-    if isinstance(depth, _abi.DeviceArray):
-        if depth.dtype != np.float32:
-            raise ValueError(f"device depth of dtype {depth.dtype}, expected float32")
-    else:
-        depth = np.asarray(depth)
-        if depth.dtype.kind not in "fiu":
-            raise ValueError(f"depth of dtype {depth.dtype}, expected a float or integer image")
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
     if rgb is not None:
         rgb_shape = _image_shape(rgb, "rgb", 3)
         if rgb_shape[:2] != (H, W):

@@ -20,10 +20,10 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .. import _abi
+from .. import _abi, rendering
 from ..certificates import CertBundle, ExpectedEffect, InfluenceCert, SupportCert
 from ..constants import D_Z, GC_CHART_ID, GC_EPS_LIFT
-from .camera_features import DEPTH_MODELS, VisualFeatureConfig
+from .camera_features import DEPTH_MODELS, VisualFeatureConfig, _depth_image
 from .camera_splats import PinholeIntrinsics
 
 MAX_POSES = _abi.GC_RENDER_MAX_VIEWS
@@ -77,7 +77,8 @@ def _check_cfg(cfg: DepthEvidenceConfig):
 
 
 def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, view_cfg, cfg, accumulate_into):
-    """Everything that can be refused without a device: (P, host poses or None, Rbc, tbc, H, W)."""
+    """Everything that can be refused without a device: (P, host poses or None, Rbc, tbc, H, W, depth_obs as
+    the device reads it)."""
     if not isinstance(intrinsics, PinholeIntrinsics):
         raise ValueError("intrinsics must be a PinholeIntrinsics")
     _check_cfg(cfg)
@@ -99,24 +100,12 @@ def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, vie
             raise ValueError("poses6 must be finite")
     if not 1 <= P <= MAX_POSES:
         raise ValueError(f"{P} poses; between 1 and {MAX_POSES} are supported")
-    Rbc = np.eye(3) if R_base_camera is None else np.asarray(R_base_camera, np.float64)
-    tbc = np.zeros(3) if t_base_camera is None else np.asarray(t_base_camera, np.float64).reshape(-1)
-    if Rbc.shape != (3, 3) or tbc.shape != (3,):
-        raise ValueError(f"R_base_camera of shape {Rbc.shape} and t_base_camera of shape {tbc.shape}: expected (3, 3), (3,)")
+    Rbc, tbc = rendering._extrinsics(R_base_camera, t_base_camera)
     if not (np.isfinite(Rbc).all() and np.isfinite(tbc).all()):
         raise ValueError("the extrinsics must be finite")
     if np.max(np.abs(Rbc.T @ Rbc - np.eye(3))) > 1e-9:
         raise ValueError("R_base_camera must be a rotation (max |R^T R - I| <= 1e-9)")
-    shape = tuple(depth_obs.shape) if isinstance(depth_obs, _abi.DeviceArray) else np.shape(depth_obs)
-    if len(shape) != 2:
-        raise ValueError(f"depth_obs of shape {shape}, expected (H, W)")
-    H, W = int(shape[0]), int(shape[1])
-    if isinstance(depth_obs, _abi.DeviceArray):
-        if depth_obs.dtype != np.float32:
-            raise ValueError(f"device depth_obs of dtype {depth_obs.dtype}, expected float32")
-    elif np.asarray(depth_obs).dtype.kind not in "fiu":
-        raise ValueError(f"depth_obs of dtype {np.asarray(depth_obs).dtype}, expected a float or integer image")
-    from .. import rendering
+    H, W, depth_obs = _depth_image(depth_obs, "depth_obs")
     rendering._check_camera_args(intrinsics, np.eye(4), H, W, view_cfg, 0)
     if accumulate_into is not None:
         try:
@@ -126,7 +115,7 @@ def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, vie
         for a, sh in ((dL, (P, D_Z, D_Z)), (dh, (P, D_Z))):
             if not isinstance(a, _abi.DeviceArray) or a.dtype != np.float64 or int(np.prod(a.shape)) != int(np.prod(sh)):
                 raise ValueError(f"accumulate_into holds float64 DeviceArrays of {P} x 22 x 22 and {P} x 22 values")
-    return P, host, Rbc, tbc, H, W
+    return P, host, Rbc, tbc, H, W, depth_obs
 
 
 def depth_pose_evidence_batched(batch_or_map, intrinsics, poses6, depth_obs, R_base_camera=None, t_base_camera=None,
@@ -146,38 +135,22 @@ def depth_pose_evidence_batched(batch_or_map, intrinsics, poses6, depth_obs, R_b
     the device (no lift) and they are what comes back. With device_out L_pose and h_pose stay
     DeviceArrays. The four device calls run with no wait between them; device poses are read once
     before the first."""
-    from .. import rendering
     view_cfg = view_cfg or rendering.CameraViewConfig()
     cfg = cfg or DepthEvidenceConfig()
-    P, host, Rbc, tbc, H, W = _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, view_cfg, cfg,
-                                          accumulate_into)
-    if isinstance(batch_or_map, rendering.DevicePrimitiveMap):
-        batch = rendering.publish_renderable(batch_or_map)
-    elif isinstance(batch_or_map, rendering.DeviceRenderableBatch):
-        batch = batch_or_map
-    elif isinstance(batch_or_map, rendering.RenderablePrimitiveBatch):
-        batch = rendering.DeviceRenderableBatch.from_host(_abi.default_context(), batch_or_map)
-    else:
-        raise ValueError(f"cannot render a {type(batch_or_map).__name__}")
+    P, host, Rbc, tbc, H, W, depth_obs = _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera,
+                                                     view_cfg, cfg, accumulate_into)
+    batch = rendering._device_batch(batch_or_map, None)
     ctx, n = batch.ctx, batch.count
     if host is None:
         host = poses6.download().reshape(P, 6)
         if not np.isfinite(host).all():
             raise ValueError("poses6 must be finite")
-    from . import se3
-    Rwb = np.asarray(se3.so3_exp(host[:, 3:], ctx=ctx), np.float64).reshape(P, 3, 3)
-    T_cw = np.zeros((P, 4, 4))
-    for p in range(P):
-        Rwc, twc = Rwb[p] @ Rbc, Rwb[p] @ tbc + host[p, :3]
-        T_cw[p, :3, :3], T_cw[p, :3, 3], T_cw[p, 3, 3] = Rwc.T, -Rwc.T @ twc, 1.0
+    T_cw = rendering.camera_from_world(host, Rbc, tbc, ctx=ctx)
     t_wb = np.ascontiguousarray(host[:, :3])
     Ks = [intrinsics] * P
     c_cfg, T_cw, K = rendering._check_camera_args(Ks, T_cw, H, W, view_cfg, n)
     ts, cap = int(view_cfg.tile_size), int(view_cfg.max_splats_per_tile)
-    if isinstance(depth_obs, _abi.DeviceArray):
-        d_obs = depth_obs
-    else:
-        d_obs = _abi.DeviceArray.from_host(ctx, np.ascontiguousarray(depth_obs, dtype=np.float32), np.float32)
+    d_obs = depth_obs if isinstance(depth_obs, _abi.DeviceArray) else _abi.DeviceArray.from_host(ctx, depth_obs, np.float32)
 
     splats = rendering.camera_splat_prep(batch, Ks, T_cw, H, W, view_cfg)
     st = rendering._CamSplatStruct(*[splats[k].ptr for k, _ in rendering._CamSplatStruct._fields_])

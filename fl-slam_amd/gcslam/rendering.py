@@ -17,7 +17,8 @@
   compositing, with a depth image beside the colour image. The raster the viewer leaves to
   jaxsplat.render_v2 is this build's and is declared in DESIGN.md §4 ("Camera view").
 
-All arithmetic runs in libgcslam (csrc/gc_render.hip, csrc/gc_camrender.hip); every argument error is
+All arithmetic runs in libgcslam (csrc/gc_render.hip, csrc/gc_camrender.hip; what they share with the depth
+evidence is csrc/gc_renderdev.h); every argument error is
 raised here before a device is asked for."""
 
 from __future__ import annotations
@@ -213,6 +214,18 @@ def publish_renderable(atlas_map: DevicePrimitiveMap, tile_ids: Optional[Sequenc
     return renderable_batch_from_view(extract_atlas_map_view(atlas_map, tile_ids, k, eps_lift=eps_lift), eps_lift)
 
 
+def _device_batch(batch_or_map, ctx) -> DeviceRenderableBatch:
+    """What the composed calls render: a device batch as it is, a map through publish_renderable, a host
+    batch uploaded to ctx (None: the default context)."""
+    if isinstance(batch_or_map, DevicePrimitiveMap):
+        return publish_renderable(batch_or_map)
+    if isinstance(batch_or_map, DeviceRenderableBatch):
+        return batch_or_map
+    if isinstance(batch_or_map, RenderablePrimitiveBatch):
+        return DeviceRenderableBatch.from_host(ctx or _abi.default_context(), batch_or_map)
+    raise ValueError(f"cannot render a {type(batch_or_map).__name__}")
+
+
 # ---------------------------------------------------------------------------------------------
 # BEV splats and the tile raster
 # ---------------------------------------------------------------------------------------------
@@ -338,14 +351,7 @@ def render_map_bev(batch_or_map: Union[DeviceRenderableBatch, RenderablePrimitiv
     _check_raster_args(cfg.tile_size, H, W, cfg.max_splats_per_tile, 0)
     _bev_cfg(viewport, cfg, fbm_seed, fbm_modulate_scale)
     P, vd = bev_views(bcfg, views)
-    if isinstance(batch_or_map, DevicePrimitiveMap):
-        batch = publish_renderable(batch_or_map)
-    elif isinstance(batch_or_map, DeviceRenderableBatch):
-        batch = batch_or_map
-    elif isinstance(batch_or_map, RenderablePrimitiveBatch):
-        batch = DeviceRenderableBatch.from_host(ctx or _abi.default_context(), batch_or_map)
-    else:
-        raise ValueError(f"cannot render a {type(batch_or_map).__name__}")
+    batch = _device_batch(batch_or_map, ctx)
     splats = bev_splat_prep(batch, viewport, P, vd, cfg, fbm_seed=fbm_seed, fbm_modulate_scale=fbm_modulate_scale)
     dev = render_ewa_tiles(splats, H, W, cfg.tile_size, cfg.max_splats_per_tile, cfg.ewa_log_clip, cfg.eps,
                            ctx=batch.ctx)
@@ -396,31 +402,42 @@ class CameraRender:
 _CamSplatStruct = _abi.STRUCTS["gc_cam_splats"]
 
 
-def camera_from_world(pose, R_base_camera=None, t_base_camera=None, *, ctx=None) -> np.ndarray:
-    """T_cw = inv(T_wb T_bc) (4, 4): what the viewer takes as its camera (view_splat_jaxsplat.py:103,
-    camera-at-body: T_bc = I, the default). pose is the body pose in the world, either the 6-vector
-    (translation, rotation vector; the rotation through ops/se3.so3_exp, on the device) or a 4 x 4
-    T_wb, which needs no device."""
-    p = np.asarray(pose, np.float64)
+def _extrinsics(R_base_camera, t_base_camera) -> Tuple[np.ndarray, np.ndarray]:
+    """(R_bc (3, 3), t_bc (3,)), the camera at the body by default; the shapes are checked here, what else a
+    caller requires of them by the caller."""
     Rbc = np.eye(3) if R_base_camera is None else np.asarray(R_base_camera, np.float64)
     tbc = np.zeros(3) if t_base_camera is None else np.asarray(t_base_camera, np.float64).reshape(-1)
     if Rbc.shape != (3, 3) or tbc.shape != (3,):
         raise ValueError(f"R_base_camera of shape {Rbc.shape} and t_base_camera of shape {tbc.shape}: expected (3, 3), (3,)")
-    if p.shape not in ((6,), (4, 4)):
+    return Rbc, tbc
+
+
+def camera_from_world(pose, R_base_camera=None, t_base_camera=None, *, ctx=None) -> np.ndarray:
+    """T_cw = inv(T_wb T_bc) (4, 4): what the viewer takes as its camera (view_splat_jaxsplat.py:103,
+    camera-at-body: T_bc = I, the default). pose is the body pose in the world, either the 6-vector
+    (translation, rotation vector; the rotation through ops/se3.so3_exp, on the device) or a 4 x 4
+    T_wb, which needs no device. P poses as (P, 6) or (P, 4, 4) give (P, 4, 4): one so3_exp call for the
+    batch, and every T_cw the bytes of the single call for its pose."""
+    p = np.asarray(pose, np.float64)
+    Rbc, tbc = _extrinsics(R_base_camera, t_base_camera)
+    if p.shape not in ((6,), (4, 4)) and not (p.ndim in (2, 3) and p.shape[1:] in ((6,), (4, 4))):
         raise ValueError(f"pose of shape {p.shape}: expected (6,) or (4, 4)")
     if not (np.isfinite(p).all() and np.isfinite(Rbc).all() and np.isfinite(tbc).all()):
         raise ValueError("the pose and the extrinsics must be finite")
-    if p.shape == (4, 4):
-        if not np.array_equal(p[3], [0.0, 0.0, 0.0, 1.0]):
+    single = p.shape in ((6,), (4, 4))
+    ps = p[None] if single else p
+    if ps.shape[1:] == (4, 4):
+        if not (ps[:, 3] == np.array([0.0, 0.0, 0.0, 1.0])).all():
             raise ValueError("the bottom row of T_wb must be (0, 0, 0, 1)")
-        Rwb, twb = p[:3, :3], p[:3, 3]
+        Rwb, twb = ps[:, :3, :3], ps[:, :3, 3]
     else:
         from .ops import se3
-        Rwb, twb = se3.so3_exp(p[3:], ctx=ctx), p[:3]
-    Rwc, twc = Rwb @ Rbc, Rwb @ tbc + twb
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = Rwc.T, -Rwc.T @ twc
-    return T
+        Rwb, twb = np.asarray(se3.so3_exp(ps[:, 3:], ctx=ctx), np.float64).reshape(-1, 3, 3), ps[:, :3]
+    T = np.tile(np.eye(4), (ps.shape[0], 1, 1))
+    for i in range(ps.shape[0]):  # 3 x 3 products one pose at a time: the bytes do not depend on the batch
+        Rwc, twc = Rwb[i] @ Rbc, Rwb[i] @ tbc + twb[i]
+        T[i, :3, :3], T[i, :3, 3] = Rwc.T, -Rwc.T @ twc
+    return T[0] if single else T
 
 
 def _camview_cfg(cfg: CameraViewConfig):
@@ -530,14 +547,7 @@ def render_map_camera(batch_or_map: Union[DeviceRenderableBatch, RenderablePrimi
     before a device is asked for: see DESIGN.md §4 for the list."""
     cfg = cfg or CameraViewConfig()
     _check_camera_args(intrinsics, T_cw, height, width, cfg, 0)
-    if isinstance(batch_or_map, DevicePrimitiveMap):
-        batch = publish_renderable(batch_or_map)
-    elif isinstance(batch_or_map, DeviceRenderableBatch):
-        batch = batch_or_map
-    elif isinstance(batch_or_map, RenderablePrimitiveBatch):
-        batch = DeviceRenderableBatch.from_host(ctx or _abi.default_context(), batch_or_map)
-    else:
-        raise ValueError(f"cannot render a {type(batch_or_map).__name__}")
+    batch = _device_batch(batch_or_map, ctx)
     splats = camera_splat_prep(batch, intrinsics, T_cw, height, width, cfg)
     dev = render_depth_tiles(splats, height, width, cfg, ctx=batch.ctx)
     names = ("images", "alpha", "depth", "n_contrib", "tile_counts", "tile_survivors", "tile_indices")

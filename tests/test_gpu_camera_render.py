@@ -146,6 +146,35 @@ def test_gpu_render_map_bev_gives_the_recorded_bytes(ctx):
 
 
 @pytest.mark.gpu
+def test_gpu_camera_view_gives_the_recorded_bytes(ctx):
+    """The camera view and the depth evidence on their recorded cases: the bytes the build gave while
+    gc_camrender.hip and gc_depthev.hip each held their own projection, view packing and raster step
+    (tests/golden/camview_parent.npz, recorded by make_camview_parent.py before they moved into
+    gc_renderdev.h). And the split of the views over launches leaves no trace: one view more than a launch
+    carries (kCamViewsPerLaunch = 16), all of them the first view of two_views, give that view's bytes."""
+    from tests.golden import make_camview_parent as MP
+    gold = np.load(MP.OUT)
+    seen = set()
+    for group, names, run in (("cam", MP.CAM_CASES, MP.run_cam), ("ev", MP.EV_CASES, MP.run_ev)):
+        for name in names:
+            for k, a in run(ctx, name).items():
+                key = f"{group}/{name}/{k}"
+                assert MP.same_as_recorded(gold, key, a), key
+                seen.add(key)
+    assert seen == MP.recorded_keys(gold) and len(seen) == 5 * 14 + 5 * 8
+    one, other = MP.run_cam(ctx, "two_views", views=[0]), MP.run_cam(ctx, "two_views", views=[1])
+    assert MP.same_as_recorded(gold, "cam/two_views/depth", np.concatenate([one["depth"], other["depth"]]))
+    many = MP.run_cam(ctx, "two_views", views=[0] * 17)
+    for k, a in many.items():
+        if k == "alphas":  # per primitive, the same for every view
+            assert a.tobytes() == one[k].tobytes()
+            continue
+        assert a.shape[0] == 17, k
+        for v in range(17):
+            assert a[v].tobytes() == one[k][0].tobytes(), (k, v)
+
+
+@pytest.mark.gpu
 def test_gpu_camera_entry_argument_errors(ctx):
     """The C entries reject what the Python layer rejects, before any launch; the context stays usable."""
     z = _abi.DeviceArray(ctx, (64,), np.float64)
