@@ -42,9 +42,14 @@ from .camera_features import VisualFeatureConfig, lift_camera_features, select_k
 from .keypoint_detector import DeviceKeypoints, Keypoints, OrbDetectorConfig, detect_keypoints
 from .depth_pose_evidence import (DepthEvidenceConfig, DepthPoseEvidenceResult, depth_pose_evidence,
                                   depth_pose_evidence_batched)
+from .photometric_pose_evidence import (PhotometricEvidenceConfig, PhotometricPoseEvidenceResult, luminance_image,
+                                        photometric_pose_evidence, photometric_pose_evidence_batched,
+                                        rgbd_pose_evidence_batched)
 from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "PhotometricEvidenceConfig", "PhotometricPoseEvidenceResult", "luminance_image", "photometric_pose_evidence",
+    "photometric_pose_evidence_batched", "rgbd_pose_evidence_batched",
     "DepthEvidenceConfig", "DepthPoseEvidenceResult", "depth_pose_evidence", "depth_pose_evidence_batched",
     "OrbDetectorConfig", "Keypoints", "DeviceKeypoints", "detect_keypoints",
     "VisualFeatureConfig", "lift_camera_features", "select_keypoints", "DeviceCameraFeatures",

@@ -76,14 +76,13 @@ def _check_cfg(cfg: DepthEvidenceConfig):
         raise ValueError(f"eps_lift must be >= 0, got {cfg.eps_lift}")
 
 
-def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, view_cfg, cfg, accumulate_into):
-    """Everything that can be refused without a device: (P, host poses or None, Rbc, tbc, H, W, depth_obs as
-    the device reads it)."""
+def _check_frame(intrinsics, poses6, R_base_camera, t_base_camera, view_cfg, what: str = "the depth evidence"):
+    """What the evidences of the camera view refuse of the poses, the extrinsics and the tiles without a
+    device: (P, host poses or None, Rbc, tbc)."""
     if not isinstance(intrinsics, PinholeIntrinsics):
         raise ValueError("intrinsics must be a PinholeIntrinsics")
-    _check_cfg(cfg)
     if int(view_cfg.tile_size) != view_cfg.tile_size or not 1 <= view_cfg.tile_size <= MAX_TILE:
-        raise ValueError(f"tile_size must be an integer in [1, {MAX_TILE}] for the depth evidence (a thread owns one "
+        raise ValueError(f"tile_size must be an integer in [1, {MAX_TILE}] for {what} (a thread owns one "
                          f"pixel), got {view_cfg.tile_size}")
     if isinstance(poses6, _abi.DeviceArray):
         if poses6.dtype != np.float64 or int(np.prod(poses6.shape)) % 6:
@@ -105,8 +104,10 @@ def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, vie
         raise ValueError("the extrinsics must be finite")
     if np.max(np.abs(Rbc.T @ Rbc - np.eye(3))) > 1e-9:
         raise ValueError("R_base_camera must be a rotation (max |R^T R - I| <= 1e-9)")
-    H, W, depth_obs = _depth_image(depth_obs, "depth_obs")
-    rendering._check_camera_args(intrinsics, np.eye(4), H, W, view_cfg, 0)
+    return P, host, Rbc, tbc
+
+
+def _check_accumulate(accumulate_into, P: int):
     if accumulate_into is not None:
         try:
             dL, dh = accumulate_into
@@ -115,6 +116,18 @@ def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, vie
         for a, sh in ((dL, (P, D_Z, D_Z)), (dh, (P, D_Z))):
             if not isinstance(a, _abi.DeviceArray) or a.dtype != np.float64 or int(np.prod(a.shape)) != int(np.prod(sh)):
                 raise ValueError(f"accumulate_into holds float64 DeviceArrays of {P} x 22 x 22 and {P} x 22 values")
+
+
+def _check_args(intrinsics, poses6, depth_obs, R_base_camera, t_base_camera, view_cfg, cfg, accumulate_into):
+    """Everything that can be refused without a device: (P, host poses or None, Rbc, tbc, H, W, depth_obs as
+    the device reads it)."""
+    if not isinstance(intrinsics, PinholeIntrinsics):
+        raise ValueError("intrinsics must be a PinholeIntrinsics")
+    _check_cfg(cfg)
+    P, host, Rbc, tbc = _check_frame(intrinsics, poses6, R_base_camera, t_base_camera, view_cfg)
+    H, W, depth_obs = _depth_image(depth_obs, "depth_obs")
+    rendering._check_camera_args(intrinsics, np.eye(4), H, W, view_cfg, 0)
+    _check_accumulate(accumulate_into, P)
     return P, host, Rbc, tbc, H, W, depth_obs
 
 

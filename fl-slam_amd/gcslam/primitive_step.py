@@ -29,6 +29,8 @@ from .constants import GC_CHART_ID
 from .map_branch import MapBranch, MapBranchFront
 from .ops.depth_pose_evidence import (MAX_POSES, DepthEvidenceConfig, depth_pose_evidence_batched,
                                       result_from_parts)
+from .ops.photometric_pose_evidence import PhotometricEvidenceConfig, rgbd_pose_evidence_batched
+from .ops.photometric_pose_evidence import result_from_parts as photo_result_from_parts
 from .ops.deskew_constant_twist import deskew_constant_twist
 from .ops.lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
 from .ops.point_budget import point_budget_resample
@@ -69,8 +71,9 @@ class PrimitiveStepResult:
     lidar_cert: np.ndarray               # the GC_LIDAR_CERT row the back ran on
     z_t: np.ndarray                      # hypothesis 0's recomposed world pose, the update's pose
     xi_body: np.ndarray                  # hypothesis 0's deskew twist
-    certs: list                          # [deskew, surfel, recency inflate, assoc, visual(, depth)]
+    certs: list                          # [deskew, surfel, recency inflate, assoc, visual(, depth(, photometric))]
     depth_parts: Optional[np.ndarray] = None  # with a depth frame: the (H, GC_DEPTHEV_PARTS) rows that were added
+    photo_parts: Optional[np.ndarray] = None  # with rgb or luminance in the frame: the luminance rows, likewise
 
 
 class PrimitiveScanStep:
@@ -110,13 +113,20 @@ class PrimitiveScanStep:
         `view_cfg` (CameraViewConfig) and `cfg` (DepthEvidenceConfig). The depth pose evidence
         (ops/depth_pose_evidence.py) of every hypothesis's linearisation pose against the map as it
         stands after MapBranch.front is added on the device into the front's L_lidar / h_lidar, and
-        hypothesis 0's certificate joins the evidence certificates. At most 32 hypotheses."""
+        hypothesis 0's certificate joins the evidence certificates. At most 32 hypotheses.
+
+        The frame may also carry `rgb` ((H, W, 3) uint8) or `luminance` ((H, W) float, NaN for a hole) of the
+        same camera, and `photo_cfg` (PhotometricEvidenceConfig): then the depth and the photometric
+        evidence (ops/photometric_pose_evidence.py: rgbd_pose_evidence_batched) are added, in that order,
+        and hypothesis 0's photometric certificate follows the depth one. `depth` stays required."""
         pipe, br = self.pipeline, self.branch
         if depth_frame is not None:
             if pipe.Hl > MAX_POSES:
                 raise ValueError(f"{pipe.Hl} hypotheses with a depth frame; at most {MAX_POSES} are supported")
             if "depth" not in depth_frame or "intrinsics" not in depth_frame:
                 raise ValueError("depth_frame needs `depth` and `intrinsics`")
+            if depth_frame.get("rgb") is not None and depth_frame.get("luminance") is not None:
+                raise ValueError("depth_frame carries `rgb` or `luminance`, not both")
         pipe.stage_scan(slot, scan)
         pipe.scan_front(slot, scan, scan_count)
         # the one small download before the map branch (the reference's own sync, pipeline.py:811):
@@ -131,16 +141,28 @@ class PrimitiveScanStep:
         inflate_cert, assoc_cert = front.certs
         vcert = visual_cert(front.vpe_cert, br.config.eps_lift, br.chart_id)
         evidence_certs = list(batch_certs) + [assoc_cert, vcert]
-        depth_certs, depth_parts = [], None
+        depth_certs, depth_parts, photo_parts = [], None, None
         if depth_frame is not None:
             dcfg = depth_frame.get("cfg") or DepthEvidenceConfig()
-            _, _, parts, render = depth_pose_evidence_batched(
-                br.atlas_map, depth_frame["intrinsics"], lin_d, depth_frame["depth"], depth_frame.get("R_base_camera"),
-                depth_frame.get("t_base_camera"), depth_frame.get("view_cfg"), dcfg,
-                accumulate_into=(front.device["L_lidar"], front.device["h_lidar"]), device_out=True)
-            depth_parts = parts
-            _, dcert, _ = result_from_parts(None, None, parts[0], render["depth"].shape[1:], dcfg.eps_lift, br.chart_id)
+            image = depth_frame.get("rgb") if depth_frame.get("rgb") is not None else depth_frame.get("luminance")
+            where = (br.atlas_map, depth_frame["intrinsics"], lin_d)
+            camera = (depth_frame.get("R_base_camera"), depth_frame.get("t_base_camera"), depth_frame.get("view_cfg"))
+            into = (front.device["L_lidar"], front.device["h_lidar"])
+            if image is None:
+                _, _, parts, render = depth_pose_evidence_batched(*where, depth_frame["depth"], *camera, dcfg,
+                                                                  accumulate_into=into, device_out=True)
+                depth_parts = parts
+            else:
+                pcfg = depth_frame.get("photo_cfg") or PhotometricEvidenceConfig(eps_lift=dcfg.eps_lift)
+                _, _, parts, render = rgbd_pose_evidence_batched(*where, depth_frame["depth"], image, *camera, dcfg,
+                                                                        pcfg, accumulate_into=into, device_out=True)
+                depth_parts, photo_parts = np.ascontiguousarray(parts[:, 0]), np.ascontiguousarray(parts[:, 1])
+            shape = render["depth"].shape[1:]
+            _, dcert, _ = result_from_parts(None, None, depth_parts[0], shape, dcfg.eps_lift, br.chart_id)
             depth_certs = [dcert]
+            if photo_parts is not None:
+                _, pcert, _ = photo_result_from_parts(None, None, photo_parts[0], shape, pcfg.eps_lift, br.chart_id)
+                depth_certs.append(pcert)
         row = lidar_cert_row(evidence_certs + depth_certs, [inflate_cert])
         pipe.set_lidar_evidence(front.device["L_lidar"], front.device["h_lidar"], row)
         pipe.scan_back()
@@ -150,4 +172,4 @@ class PrimitiveScanStep:
         return PrimitiveStepResult(front=front, update=upd, combined=pipe.combined(), lidar_cert=row, z_t=z_t,
                                    xi_body=xi0.copy(),
                                    certs=list(batch_certs) + [inflate_cert, assoc_cert, vcert] + depth_certs,
-                                   depth_parts=depth_parts)
+                                   depth_parts=depth_parts, photo_parts=photo_parts)

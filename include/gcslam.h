@@ -1622,6 +1622,71 @@ int32_t gc_depth_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc
                                double eps_lift, int32_t accumulate, double* d_L_pose, double* d_h_pose,
                                double* d_parts, double* d_residual, double* d_weight);
 
+/* ------------------------------------------------------------------------------------------
+ * Photometric pose evidence from the camera view: one luminance channel of the rendered colour against
+ * an observed image, in the depth evidence's tangent convention, coordinates and output layout (this
+ * build's, DESIGN.md §4, "Photometric pose evidence"). The luminance of a colour (r, g, b) is
+ * y = (w_r r + w_g g) + w_b b for a weight triple w (host, 3 doubles; any finite values; the keypoint
+ * detector's grey is (4899, 9617, 1868) / 16384). The residual is against Y / A, the rendered luminance
+ * over the coverage, as the rendered depth is D / A: it does not read the background colour.
+ * ------------------------------------------------------------------------------------------ */
+
+/* d_rgb8 (H, W, 3) uint8 as d_lum (H, W) float32 = ((w_r R + w_g G) + w_b B) / 255, the sum in f64. No
+   wait. GC_ERR_ARG before the launch for H or W outside [1, 16384], a non-finite weight or NULL pointers. */
+int32_t gc_image_luminance(gc_ctx* ctx, const uint8_t* d_rgb8, int32_t H, int32_t W, const double* h_weights,
+                           float* d_lum);
+
+/* The luminance of gc_camera_splat_prep's colour rows and its six pose tangents, per (pose, primitive);
+   the arguments as gc_camera_splat_jvp takes them. d_lum (n_poses, n) = y of splats->colors (the forward's
+   bits, shading included). d_dlum (n_poses, n, 6) = (w . batch->color) ds_k with ds the tangent of the vMF
+   shading at vd = c - mu, c the camera centre: dc = e_k for dt_k and e_k x (c - t_wb) for dtheta_k;
+   n = |vd|, nv = n + 1e-12, v = vd / nv, dv = dc / nv - vd (vd . dc) / (n nv^2);
+   ds = (1 / (1 + mean kappa)) (1 / L) sum_l exp(kappa_l (m_l . v - 1)) kappa_l (m_l . dv) with
+   m_l = eta_l / (kappa_l + 1e-12), kappa_l = |eta_l| (a lobe with eta = 0 contributes 0). Rows that are not
+   valid have lum = 0 and dlum = 0; shade = 0 gives dlum = 0. No wait. GC_ERR_ARG before any launch for what
+   gc_camera_splat_jvp refuses, n_lobes outside [1, 8], a non-finite weight or NULL pointers. n = 0
+   launches nothing. */
+int32_t gc_camera_shade_jvp(gc_ctx* ctx, const gc_render_batch* batch, int64_t n, int32_t n_poses, const double* h_T_cw,
+                            const double* h_t_wb, const double* h_intrinsics, int32_t H, int32_t W,
+                            const gc_camview_cfg* cfg, const gc_cam_splats* splats, const double* h_weights, double* d_lum,
+                            double* d_dlum);
+
+/* Gaussian pose evidence of an observed luminance image d_lum_obs (H, W; float32, NaN or an infinity
+   marks a hole; device; shared by the poses), per pose, over the lists and beside the coverage d_alpha of
+   gc_render_depth_tiles, with gc_depth_pose_evidence's raster, branches and order and the state
+   (T, Y, dT[6], dY[6]): Y += T a y; dY += dT a y + T da y + T a dy (y, dy: gc_camera_shade_jvp's). A pixel
+   is used where lum_obs is finite and A > eps; there r = Y / A - lum_obs, J = (dY A + Y dT) / A^2,
+   u = (nu + 1) / (nu + (r / sigma)^2) (use_robust 0: u = 1), w = A u / sigma^2. L6, h6, cost, n_used,
+   sum_cov, sum_w, d_parts (n_poses, GC_DEPTHEV_PARTS), d_L_pose, d_h_pose, accumulate, d_residual and
+   d_weight as in gc_depth_pose_evidence; d_lum_render (n_poses, H, W; may be NULL) receives Y / A, 0 where
+   A <= eps. No wait; uses the context's scratch; bitwise reproducible. n = 0: no raster. GC_ERR_ARG
+   before any launch for that entry's frame bounds, an invalid configuration, sigma <= 0, use_robust with
+   nu <= 0, a non-finite parameter, eps_lift < 0 or NULL pointers. */
+int32_t gc_photo_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc_cam_splats* splats,
+                               const double* d_dmeans_px, const double* d_dSigmas_inv, const double* d_lum,
+                               const double* d_dlum, int32_t H, int32_t W, int32_t tile_size, int32_t cap,
+                               const gc_camview_cfg* cfg, const int32_t* d_tile_counts, const int32_t* d_tile_indices,
+                               const double* d_alpha, const float* d_lum_obs, double sigma, int32_t use_robust,
+                               double robust_nu, double eps_lift, int32_t accumulate, double* d_L_pose, double* d_h_pose,
+                               double* d_parts, double* d_lum_render, double* d_residual, double* d_weight);
+
+/* Both evidences in one pass over the lists (q, the exponential, dq and da are shared): the arguments of
+   gc_depth_pose_evidence and of gc_photo_pose_evidence. d_parts (n_poses, 2, GC_DEPTHEV_PARTS): the depth
+   row, then the luminance row, each the bytes of its own entry. The depth's L6 and h6 and then the
+   luminance's are added into d_L_pose / d_h_pose, two successive additions in that order; accumulate 0:
+   one eps_lift I is added, with the depth's. The same bytes as gc_depth_pose_evidence followed by
+   gc_photo_pose_evidence with accumulate 1. GC_ERR_ARG as either entry. */
+int32_t gc_rgbd_pose_evidence(gc_ctx* ctx, int32_t n_poses, int64_t n, const gc_cam_splats* splats,
+                              const double* d_dmeans_px, const double* d_ddepths, const double* d_dSigmas_inv,
+                              const double* d_lum, const double* d_dlum, int32_t H, int32_t W, int32_t tile_size,
+                              int32_t cap, const gc_camview_cfg* cfg, const int32_t* d_tile_counts,
+                              const int32_t* d_tile_indices, const double* d_alpha, const double* d_depth,
+                              const float* d_depth_obs, int32_t depth_model, double sigma0, double slope, double min_depth,
+                              double max_depth, int32_t depth_use_robust, double depth_robust_nu, const float* d_lum_obs,
+                              double lum_sigma, int32_t lum_use_robust, double lum_robust_nu, double eps_lift,
+                              int32_t accumulate, double* d_L_pose, double* d_h_pose, double* d_parts, double* d_residual,
+                              double* d_weight, double* d_lum_render, double* d_lum_residual, double* d_lum_weight);
+
 #ifdef __cplusplus
 }
 #endif
