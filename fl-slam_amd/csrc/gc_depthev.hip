@@ -553,22 +553,26 @@ int ev_evidence(gc_ctx* ctx, const EvDepthIn* dp, const EvLumIn* lp, int32_t n_p
   const size_t px = (size_t)n_poses * H * W;
   const int stride = (dp && lp) ? 2 * kEvParts : kEvParts;
   double* const parts_y = d_parts + (dp ? kEvParts : 0);
+  // one k_ev_final per channel given, over the T tiles' rows of its partial sums
+  auto finals = [&](int T, const double* partial_d, const double* partial_y) -> int {
+    if (dp) {
+      hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, T, partial_d, eps_lift,
+                         (int)(accumulate != 0), d_L_pose, d_h_pose, d_parts, stride);
+      GC_LAUNCH_CHECK(ctx);
+    }
+    if (lp) {
+      hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, T, partial_y, eps_lift,
+                         (int)(dp || accumulate != 0), d_L_pose, d_h_pose, parts_y, stride);
+      GC_LAUNCH_CHECK(ctx);
+    }
+    return GC_OK;
+  };
   if (n == 0) {  // no raster over an empty range: the sums over no tile
     double* const images[5] = {dp ? dp->residual : nullptr, dp ? dp->weight : nullptr, lp ? lp->render : nullptr,
                                lp ? lp->residual : nullptr, lp ? lp->weight : nullptr};
     for (double* im : images)
       if (im) GC_HIP(ctx, hipMemsetAsync(im, 0, sizeof(double) * px, st));
-    if (dp) {
-      hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, 0, (const double*)nullptr, eps_lift,
-                         (int)(accumulate != 0), d_L_pose, d_h_pose, d_parts, stride);
-      GC_LAUNCH_CHECK(ctx);
-    }
-    if (lp) {
-      hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, 0, (const double*)nullptr, eps_lift,
-                         (int)(dp || accumulate != 0), d_L_pose, d_h_pose, parts_y, stride);
-      GC_LAUNCH_CHECK(ctx);
-    }
-    return GC_OK;
+    return finals(0, nullptr, nullptr);
   }
   GC_CHECK_ARG(ctx, splats && splats->means_px && splats->Sigmas_inv && splats->alphas && (!dp || splats->depths),
                "NULL splat field");
@@ -601,17 +605,7 @@ int ev_evidence(gc_ctx* ctx, const EvDepthIn* dp, const EvLumIn* lp, int32_t n_p
   else if (dp) hipLaunchKernelGGL(k_ev_raster<kEvDepth>, dim3((unsigned)segs), dim3(kRdT), 0, st, A);
   else hipLaunchKernelGGL(k_ev_raster<kEvLum>, dim3((unsigned)segs), dim3(kRdT), 0, st, A);
   GC_LAUNCH_CHECK(ctx);
-  if (dp) {
-    hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, (int)G.T, (const double*)partial, eps_lift,
-                       (int)(accumulate != 0), d_L_pose, d_h_pose, d_parts, stride);
-    GC_LAUNCH_CHECK(ctx);
-  }
-  if (lp) {
-    hipLaunchKernelGGL(k_ev_final, dim3((unsigned)n_poses), dim3(kRdT), 0, st, (int)G.T, partial_y, eps_lift,
-                       (int)(dp || accumulate != 0), d_L_pose, d_h_pose, parts_y, stride);
-    GC_LAUNCH_CHECK(ctx);
-  }
-  return GC_OK;
+  return finals((int)G.T, partial, partial_y);
 }
 
 // the checks gc_camera_splat_jvp and gc_camera_shade_jvp share, and the packed views

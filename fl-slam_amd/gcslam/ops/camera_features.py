@@ -111,7 +111,7 @@ def select_keypoints(responses, max_features: int) -> np.ndarray:
     return np.sort(order[:k]).astype(np.int64)
 
 
-def _image_shape(x, what: str, channels: Optional[int]):
+def image_shape(x, what: str, channels: Optional[int]):
     sh = tuple(int(v) for v in (x.shape if isinstance(x, _abi.DeviceArray) else np.shape(x)))
     want = 2 if channels is None else 3
     if len(sh) != want or (channels is not None and sh[2] != channels):
@@ -119,10 +119,10 @@ def _image_shape(x, what: str, channels: Optional[int]):
     return sh
 
 
-def _depth_image(depth, what: str):
+def depth_image(depth, what: str):
     """(H, W, image) of a depth image called `what`: the float32 DeviceArray itself, or the host image as
     contiguous float32 (another float or integer dtype is converted)."""
-    H, W = _image_shape(depth, what, None)
+    H, W = image_shape(depth, what, None)
     if isinstance(depth, _abi.DeviceArray):
         if depth.dtype != np.float32:
             raise ValueError(f"device {what} of dtype {depth.dtype}, expected float32")
@@ -173,11 +173,11 @@ def lift_camera_features(depth, rgb, keypoints_uv, responses, intrinsics,
     except (TypeError, ValueError):
         raise ValueError("intrinsics must be a PinholeIntrinsics or [fx, fy, cx, cy]") from None
     h_k = _intr_vector(fx, fy, cx, cy)
-    H, W, depth = _depth_image(depth, "depth")
+    H, W, depth = depth_image(depth, "depth")
     if H < 1 or W < 1 or H * W > MAX_PIXELS:
         raise ValueError(f"a depth image of {H} x {W}; H and W must be >= 1 and H W <= 2^26")
     if rgb is not None:
-        rgb_shape = _image_shape(rgb, "rgb", 3)
+        rgb_shape = image_shape(rgb, "rgb", 3)
         if rgb_shape[:2] != (H, W):
             raise ValueError(f"rgb of shape {rgb_shape} for a depth image of {H} x {W}")
         if not isinstance(rgb, _abi.DeviceArray):

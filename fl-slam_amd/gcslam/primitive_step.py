@@ -27,10 +27,10 @@ import numpy as np
 from .certificates import CertBundle, InfluenceCert, SupportCert, aggregate_certificates
 from .constants import GC_CHART_ID
 from .map_branch import MapBranch, MapBranchFront
-from .ops.depth_pose_evidence import (MAX_POSES, DepthEvidenceConfig, depth_pose_evidence_batched,
-                                      result_from_parts)
+from .ops.depth_pose_evidence import MAX_POSES, DepthEvidenceConfig, depth_pose_evidence_batched
+from .ops.depth_pose_evidence import result_from_parts as depth_result
 from .ops.photometric_pose_evidence import PhotometricEvidenceConfig, rgbd_pose_evidence_batched
-from .ops.photometric_pose_evidence import result_from_parts as photo_result_from_parts
+from .ops.photometric_pose_evidence import result_from_parts as photo_result
 from .ops.deskew_constant_twist import deskew_constant_twist
 from .ops.lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
 from .ops.point_budget import point_budget_resample
@@ -143,7 +143,7 @@ class PrimitiveScanStep:
         evidence_certs = list(batch_certs) + [assoc_cert, vcert]
         depth_certs, depth_parts, photo_parts = [], None, None
         if depth_frame is not None:
-            dcfg = depth_frame.get("cfg") or DepthEvidenceConfig()
+            dcfg, pcfg = depth_frame.get("cfg") or DepthEvidenceConfig(), None
             image = depth_frame.get("rgb") if depth_frame.get("rgb") is not None else depth_frame.get("luminance")
             where = (br.atlas_map, depth_frame["intrinsics"], lin_d)
             camera = (depth_frame.get("R_base_camera"), depth_frame.get("t_base_camera"), depth_frame.get("view_cfg"))
@@ -158,11 +158,9 @@ class PrimitiveScanStep:
                                                                         pcfg, accumulate_into=into, device_out=True)
                 depth_parts, photo_parts = np.ascontiguousarray(parts[:, 0]), np.ascontiguousarray(parts[:, 1])
             shape = render["depth"].shape[1:]
-            _, dcert, _ = result_from_parts(None, None, depth_parts[0], shape, dcfg.eps_lift, br.chart_id)
-            depth_certs = [dcert]
-            if photo_parts is not None:
-                _, pcert, _ = photo_result_from_parts(None, None, photo_parts[0], shape, pcfg.eps_lift, br.chart_id)
-                depth_certs.append(pcert)
+            for read, rows, cfg in ((depth_result, depth_parts, dcfg), (photo_result, photo_parts, pcfg)):
+                if rows is not None:  # hypothesis 0's certificate
+                    depth_certs.append(read(None, None, rows[0], shape, cfg.eps_lift, br.chart_id)[1])
         row = lidar_cert_row(evidence_certs + depth_certs, [inflate_cert])
         pipe.set_lidar_evidence(front.device["L_lidar"], front.device["h_lidar"], row)
         pipe.scan_back()

@@ -182,6 +182,29 @@ def test_gpu_joint_accumulation_is_the_two_single_ones_in_order(ctx):
     assert not np.array_equal(outs[0][0][:, :6, :6], L0[:, :6, :6])
 
 
+def test_gpu_evidence_gives_the_recorded_bytes(ctx):
+    """The photometric and the joint routes, and accumulate_into and device_out on the three routes: the bytes the
+    build gave while depth_pose_evidence.py and photometric_pose_evidence.py each held their own host driver
+    (tests/golden/evidence_parent.npz, recorded by make_evidence_parent.py before they became
+    camview_pose_evidence.py's). L_pose, h_pose and parts byte for byte, the per-splat arrays and the images by
+    their SHA-256."""
+    from tests.golden import make_evidence_parent as MP
+    gold = np.load(MP.OUT)
+    seen = set()
+    for route, name in MP.RUNS:
+        got = MP.run(ctx, route, name)
+        digests = got.pop("sha256")
+        want = gold[f"{route}/{name}/sha256"]
+        kind = MP.DEPTH_DIGESTS if route == "acc_depth" else MP.PHOTO_DIGESTS if route.endswith("photo") else MP.JOINT_DIGESTS
+        assert want.shape == digests.shape == (len(kind), 32)
+        for k, a, b in zip(kind, digests, want):
+            assert a.tobytes() == b.tobytes(), (route, name, k)
+        for k, a in got.items():
+            assert MP.same_as_recorded(gold, f"{route}/{name}/{k}", a), (route, name, k)
+        seen.update(f"{route}/{name}/{k}" for k in list(got) + ["sha256"])
+    assert seen == set(gold.files) and len(seen) == 18 * 4
+
+
 # ------------------------------------------------------------------------------------------ reproducibility
 def test_gpu_photo_evidence_reproducible_and_rows(ctx):
     """Two calls give identical bytes; a row of the batched call is the single call for that pose; a device

@@ -294,3 +294,38 @@ def test_luminance_image_refuses_before_a_device(kw, word):
     args.update(kw)
     with pytest.raises(ValueError, match=word):
         luminance_image(**args)
+
+
+@pytest.mark.parametrize("module, operator, trigger, cls", [
+    ("depth_pose_evidence", "depth_pose_evidence", "render_depth_residual", "DepthPoseEvidenceResult"),
+    ("photometric_pose_evidence", "photometric_pose_evidence", "render_photometric_residual", "PhotometricPoseEvidenceResult")])
+def test_result_from_parts_reads_a_parts_row(module, operator, trigger, cls):
+    """Both result_from_parts on synthetic 46-value rows [L6 (36) | h6 (6) | cost | n_used | sum_cov | sum_w]: the
+    fields come from the documented offsets, the certificate is approximate with the operator's own residual
+    trigger, and exact with a zero effect when no pixel is used; the anchor and the objective are the operator's."""
+    import importlib
+    import gcslam.ops
+    mod = importlib.import_module("gcslam.ops." + module)
+    row = np.random.default_rng(9).normal(size=46)
+    assert row.shape == (46,)
+    row[42:46] = 3.25, 200.0, 150.5, 180.25
+    L, h = np.ones((22, 22)), np.ones(22)
+    res, cert, eff = mod.result_from_parts(L, h, row, (16, 32), 1e-7, "chart")
+    assert type(res) is getattr(gcslam.ops, cls) is getattr(mod, cls)
+    assert res.L_pose is L and res.h_pose is h
+    assert np.array_equal(res.L6, row[:36].reshape(6, 6)) and np.array_equal(res.h6, row[36:42])
+    assert (res.total_weighted_cost, res.n_used, res.sum_coverage, res.sum_weight) == (3.25, 200, 150.5, 180.25)
+    assert isinstance(res.n_used, int)
+    assert not cert.exact and cert.approximation_triggers == ["linearization", trigger]
+    assert cert.chart_id == "chart" and cert.anchor_id == operator
+    assert cert.support.support_frac == 200 / (16 * 32.0) and cert.support.ess_total == 150.5
+    assert cert.influence.lift_strength == 1e-7
+    assert eff.objective_name == operator and eff.predicted == eff.realized == 3.25
+    row[0] = 7.0   # the results hold copies of the row
+    assert res.L6[0, 0] != 7.0
+    _, cert_a, _ = mod.result_from_parts(None, None, row, (16, 32), anchor_id="elsewhere")
+    assert cert_a.anchor_id == "elsewhere"
+    row[43] = 0.0
+    res0, cert0, eff0 = mod.result_from_parts(None, None, row, (16, 32))
+    assert res0.n_used == 0 and cert0.exact and cert0.anchor_id == operator
+    assert eff0.objective_name == operator and eff0.predicted == 0.0 and eff0.realized == 0.0

@@ -10,7 +10,8 @@ depth frame and an rgb image rendered at a slightly moved pose.
 
 All are device times between events on the context's stream, in one session, the stream drained before each
 sample; warm-ups first, then the median [p10-p90]. The prep, the tangents and the forward raster are made
-once per shape (time_depth_evidence.py times them). The joint entry is the default of
+once per shape by the first half of the wrappers' driver (camview_pose_evidence.prepare; time_depth_evidence.py
+times them), and the entries are called as the driver calls them (evidence_call). The joint entry is the default of
 rgbd_pose_evidence_batched only where its median is below the sum's by more than the two p10-p90 spreads
 together: the last column says so per shape.
 
@@ -18,7 +19,6 @@ together: the last column says so per shape.
 """
 
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -33,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gcslam import _abi  # noqa: E402
 from gcslam import rendering as R  # noqa: E402
 from gcslam.ops import DepthEvidenceConfig, PhotometricEvidenceConfig, luminance_image  # noqa: E402
+from gcslam.ops import camview_pose_evidence as camview  # noqa: E402
 from time_camera_render import H, K, W, build, summary  # noqa: E402
 from time_depth_evidence import poses6  # noqa: E402
 
@@ -47,8 +48,6 @@ def main():
     a = ap.parse_args()
     ctx = _abi.default_context()
     vcfg, ecfg, pcfg = R.CameraViewConfig(), DepthEvidenceConfig(robust_nu=4.0), PhotometricEvidenceConfig(robust_nu=4.0)
-    c_cfg = R._camview_cfg(vcfg)
-    w = np.array(pcfg.weights, np.float64)
     ts, cap = int(vcfg.tile_size), int(vcfg.max_splats_per_tile)
     ev = [_abi.Event(ctx) for _ in range(5)]
     names = ("shade", "depth", "photo", "rgbd")
@@ -62,38 +61,22 @@ def main():
         l_obs = luminance_image(rgb, ctx=ctx, device_out=True)
         for P in a.poses:
             X = poses6(P)
-            T_cw = np.stack([R.camera_from_world(x, ctx=ctx) for x in X])
-            t_wb, Ks = np.ascontiguousarray(X[:, :3]), [K] * P
-            Kh = np.array([[K.fx, K.fy, K.cx, K.cy]] * P, np.float64)
-            dm, dz, dS, dl, ddl, dL, dh, pd, py, pj = _abi.alloc_many(
-                ctx, [(P, n, 6, 2), (P, n, 6), (P, n, 6, 3), (P, n), (P, n, 6), (P, 22, 22), (P, 22),
-                      (P, _abi.GC_DEPTHEV_PARTS), (P, _abi.GC_DEPTHEV_PARTS), (P, 2, _abi.GC_DEPTHEV_PARTS)])
-            splats = R.camera_splat_prep(batch, Ks, T_cw, H, W, vcfg)
-            st = R._CamSplatStruct(*[splats[k].ptr for k, _ in R._CamSplatStruct._fields_])
-            views = (C.byref(batch.struct), n, P, T_cw.ctypes.data, t_wb.ctypes.data, Kh.ctypes.data, H, W, C.byref(c_cfg),
-                     C.byref(st))
-            _abi.call("gc_camera_splat_jvp", ctx.handle, *views, dm.ptr, dz.ptr, dS.ptr, ctx=ctx)
-            dev = R.render_depth_tiles(splats, H, W, vcfg, ctx=ctx)
-            frame = (H, W, ts, cap, C.byref(c_cfg), dev["tile_counts"].ptr, dev["tile_indices"].ptr, dev["alpha"].ptr)
-            d_args = (dev["depth"].ptr, d_obs.ptr, 0, ecfg.depth_sigma0, ecfg.depth_sigma_slope, ecfg.min_depth_m,
-                      ecfg.max_depth_m, 1, ecfg.robust_nu)
-            y_args = (l_obs.ptr, pcfg.sigma, 1, pcfg.robust_nu)
-            out = (ecfg.eps_lift, 0, dL.ptr, dh.ptr)
+            f = camview.prepare(batch, K, X, (d_obs, ecfg), (l_obs, pcfg), view_cfg=vcfg)   # the driver's first half
+            dL, dh, pd, py, pj = _abi.alloc_many(ctx, [(P, 22, 22), (P, 22), (P, _abi.GC_DEPTHEV_PARTS),
+                                                       (P, _abi.GC_DEPTHEV_PARTS), (P, 2, _abi.GC_DEPTHEV_PARTS)])
+            dl, ddl = f.render["lum"], f.render["dlum"]
             samples = {k: [] for k in names + ("sum",)}
             first = None
             for it in range(a.warmup + a.iters):
                 ctx.sync()
                 ev[0].record()
-                _abi.call("gc_camera_shade_jvp", ctx.handle, *views, w.ctypes.data, dl.ptr, ddl.ptr, ctx=ctx)
+                _abi.call("gc_camera_shade_jvp", ctx.handle, *f.views, f.weights.ctypes.data, dl.ptr, ddl.ptr, ctx=ctx)
                 ev[1].record()
-                _abi.call("gc_depth_pose_evidence", ctx.handle, P, n, C.byref(st), dm.ptr, dz.ptr, dS.ptr, *frame, *d_args,
-                          *out, pd.ptr, None, None, ctx=ctx)
+                camview.evidence_call(f, "depth", 0, dL, dh, pd)
                 ev[2].record()
-                _abi.call("gc_photo_pose_evidence", ctx.handle, P, n, C.byref(st), dm.ptr, dS.ptr, dl.ptr, ddl.ptr, *frame,
-                          *y_args, *out, py.ptr, None, None, None, ctx=ctx)
+                camview.evidence_call(f, "photo", 0, dL, dh, py)
                 ev[3].record()
-                _abi.call("gc_rgbd_pose_evidence", ctx.handle, P, n, C.byref(st), dm.ptr, dz.ptr, dS.ptr, dl.ptr, ddl.ptr,
-                          *frame, *d_args, *y_args, *out, pj.ptr, None, None, None, None, None, ctx=ctx)
+                camview.evidence_call(f, "rgbd", 0, dL, dh, pj)
                 ev[4].record()
                 ctx.sync()
                 rows = pj.download()
