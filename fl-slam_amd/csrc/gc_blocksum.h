@@ -11,8 +11,8 @@
 //                partial the partial of lane ^ off, which covers a disjoint set of lanes; a + b = b + a,
 //                so both partners, and in the end all lanes, hold the same bits), then the waves in wave
 //                order, then the workgroups by sum_partials. Used by gc_assoc.hip, gc_vpe.hip,
-//                gc_surfel.hip, gc_camsplat.hip and, for the wave step alone, gc_mapops.hip (whose
-//                block_partials adds its four waves pairwise and says why).
+//                gc_surfel.hip, gc_camsplat.hip and, for the wave step alone, gc_depthsurfel.hip (one wave
+//                per cell) and gc_mapops.hip (whose block_partials adds its four waves pairwise and says why).
 //
 // The run-to-run bit identity of these operators, and a batch row being equal to the single call, rest
 // on the order written here: lane-local sums in index order first (the caller's loop), no floating-point

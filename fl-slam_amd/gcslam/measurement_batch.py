@@ -28,7 +28,9 @@ BATCH_ARRAYS = dict(Lambdas=((3, 3), np.float64, np.float64), thetas=((3,), np.f
 class MeasurementBatch:
     """measurement_batch.py:68-134. With device_out the nine array fields are DeviceArrays (the same
     objects as in ``device``); otherwise host arrays. ``lidar_slot_cells`` (n_surfel, int32; -1 past
-    n_lidar_valid) is a diagnostic of the device extraction: the hash cell each LiDAR slot came from."""
+    n_lidar_valid) is a diagnostic of the device extraction: the hash cell each LiDAR slot came from;
+    ``depth_slot_cells`` (n_feat, int32) likewise the image cell of every camera row that
+    ops.extract_depth_surfels wrote, -1 for the rows it did not."""
     Lambdas: np.ndarray         # (n_total, 3, 3)
     thetas: np.ndarray          # (n_total, 3)
     etas: np.ndarray            # (n_total, GC_VMF_N_LOBES, 3)
@@ -44,6 +46,7 @@ class MeasurementBatch:
     n_lidar_valid: int
     device: Optional[dict] = None
     lidar_slot_cells: Optional[np.ndarray] = None
+    depth_slot_cells: Optional[np.ndarray] = None
 
     @property
     def n_total(self) -> int:

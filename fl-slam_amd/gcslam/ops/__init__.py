@@ -35,6 +35,7 @@ from .imu_odom_evidence import (ImuDependenceInflationResult, ImuGyroEvidenceRes
 from .visual_pose_evidence import (VisualPoseEvidenceResult, build_visual_pose_evidence_22d, visual_pose_evidence,
                                    visual_pose_evidence_batched)
 from .lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
+from .depth_surfel_extraction import DepthSurfelConfig, extract_depth_surfels
 from .camera_splats import (CameraFeatures, CameraSplatDiagnostics, DeviceCameraFeatures,
                             LidarCameraDepthFusionConfig, PinholeIntrinsics, camera_measurement_batch,
                             feature_list_to_camera_batch, lidar_depth_evidence, measurement_batch_from_camera_splats)
@@ -48,6 +49,7 @@ from .photometric_pose_evidence import (PhotometricEvidenceConfig, PhotometricPo
 from ..measurement_batch import MeasurementBatch, create_empty_measurement_batch
 
 __all__ = [
+    "DepthSurfelConfig", "extract_depth_surfels",
     "PhotometricEvidenceConfig", "PhotometricPoseEvidenceResult", "luminance_image", "photometric_pose_evidence",
     "photometric_pose_evidence_batched", "rgbd_pose_evidence_batched",
     "DepthEvidenceConfig", "DepthPoseEvidenceResult", "depth_pose_evidence", "depth_pose_evidence_batched",

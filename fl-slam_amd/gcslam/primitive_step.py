@@ -32,6 +32,7 @@ from .ops.depth_pose_evidence import result_from_parts as depth_result
 from .ops.photometric_pose_evidence import PhotometricEvidenceConfig, rgbd_pose_evidence_batched
 from .ops.photometric_pose_evidence import result_from_parts as photo_result
 from .ops.deskew_constant_twist import deskew_constant_twist
+from .ops.depth_surfel_extraction import DepthSurfelConfig, extract_depth_surfels
 from .ops.lidar_surfel_extraction import SurfelExtractionConfig, extract_lidar_surfels
 from .ops.point_budget import point_budget_resample
 from .pipeline import BatchedScanPipeline
@@ -71,7 +72,7 @@ class PrimitiveStepResult:
     lidar_cert: np.ndarray               # the GC_LIDAR_CERT row the back ran on
     z_t: np.ndarray                      # hypothesis 0's recomposed world pose, the update's pose
     xi_body: np.ndarray                  # hypothesis 0's deskew twist
-    certs: list                          # [deskew, surfel, recency inflate, assoc, visual(, depth(, photometric))]
+    certs: list                          # [deskew, surfel(, depth surfels), recency inflate, assoc, visual(, depth(, photometric))]
     depth_parts: Optional[np.ndarray] = None  # with a depth frame: the (H, GC_DEPTHEV_PARTS) rows that were added
     photo_parts: Optional[np.ndarray] = None  # with rgb or luminance in the frame: the luminance rows, likewise
 
@@ -103,6 +104,18 @@ class PrimitiveScanStep:
                                                       chart_id=chart, ctx=ctx, device_out=True)
         return batch, dsk_cert, surfel_cert
 
+    def depth_surfels(self, batch, depth_frame: dict, timestamp: float):
+        """The camera slice of the scan's batch filled from the RGB-D frame (ops/depth_surfel_extraction.py),
+        after the camera rows the batch already holds. Returns (batch, depth surfel cert)."""
+        cfg = depth_frame["surfels"]
+        if not isinstance(cfg, DepthSurfelConfig):
+            cfg = DepthSurfelConfig(n_feat=int(batch.n_feat), n_surfel=int(batch.n_surfel))
+        batch, cert, _ = extract_depth_surfels(
+            depth_frame["depth"], depth_frame.get("rgb"), depth_frame["intrinsics"], depth_frame.get("R_base_camera"),
+            depth_frame.get("t_base_camera"), float(depth_frame.get("timestamp", timestamp)), cfg, base_batch=batch,
+            chart_id=self.branch.chart_id, ctx=self.pipeline.ctx, device_out=True)
+        return batch, cert
+
     def run(self, slot: int, scan: dict, scan_count: int, timestamp: float, measurement_batch=None,
             batch_certs: Sequence[CertBundle] = (), depth_frame: Optional[dict] = None) -> PrimitiveStepResult:
         """One scan. With measurement_batch the caller's batch is used (batch_certs: its deskew / surfel
@@ -118,7 +131,15 @@ class PrimitiveScanStep:
         The frame may also carry `rgb` ((H, W, 3) uint8) or `luminance` ((H, W) float, NaN for a hole) of the
         same camera, and `photo_cfg` (PhotometricEvidenceConfig): then the depth and the photometric
         evidence (ops/photometric_pose_evidence.py: rgbd_pose_evidence_batched) are added, in that order,
-        and hypothesis 0's photometric certificate follows the depth one. `depth` stays required."""
+        and hypothesis 0's photometric certificate follows the depth one. `depth` stays required.
+
+        With `surfels` (True, or a DepthSurfelConfig whose budgets are the batch's) the frame also feeds the
+        map: once the scan's batch is there (built or the caller's) and before MapBranch.front, the free rows
+        of its camera slice are filled with the coloured surfels of `depth` and `rgb`
+        (ops/depth_surfel_extraction.py; a `luminance`-only frame gives rows without colour), at the frame's
+        extrinsics and its `timestamp` (default: the scan's). Their certificate follows the surfel one in
+        batch_certs, so it is in the GC_LIDAR_CERT aggregate and in `certs`. Without the key nothing of the
+        step changes."""
         pipe, br = self.pipeline, self.branch
         if depth_frame is not None:
             if pipe.Hl > MAX_POSES:
@@ -137,6 +158,9 @@ class PrimitiveScanStep:
         if measurement_batch is None:
             measurement_batch, dsk_cert, surfel_cert = self.measurement_batch(scan, xi0, ess0)
             batch_certs = [dsk_cert, surfel_cert]
+        if depth_frame is not None and depth_frame.get("surfels"):
+            measurement_batch, ds_cert = self.depth_surfels(measurement_batch, depth_frame, timestamp)
+            batch_certs = list(batch_certs) + [ds_cert]
         front = br.front(measurement_batch, center, lin_d, int(scan_count), device_out=True)
         inflate_cert, assoc_cert = front.certs
         vcert = visual_cert(front.vpe_cert, br.config.eps_lift, br.chart_id)

@@ -1172,6 +1172,51 @@ int32_t gc_extract_lidar_surfels(gc_ctx* ctx, int64_t N, const double* d_points,
                                  int32_t* d_source_indices, uint8_t* d_valid_mask, double* d_timestamps_out,
                                  double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid);
 
+/* RGB-D surfel extraction (this build's; the reference's camera path is ORB-only; DESIGN.md §4, "Depth
+   surfels"): coloured rows of the camera slice (sources = 0) of a MeasurementBatch, in the base frame,
+   from one depth image d_depth (H, W; float32, metres; device) and its rgb image d_rgb8 (H, W, 3; uint8;
+   device; may be NULL). h_intrinsics (host) = [fx, fy, cx, cy]; h_R_base_camera (9, row-major) and
+   h_t_base_camera (3) on the host; n_camera_valid_in the camera rows already used. cfg (host) is
+   gc_surfel_cfg, read for n_feat, n_surfel, wishart_*, kappa_*, eig_min, eps_lift and n_lobes; its hash-grid
+   members, min_points_per_voxel and sensor_noise_var_per_axis are ignored.
+   Cells: cell_px x cell_px pixel blocks in row-major order, n_cx = ceil(W / cell_px), cell id = cy n_cx +
+   cx; H and W need not be multiples, and the pixels of an edge cell outside the image are missing. A pixel
+   is used where its depth z is finite and min_depth < z < max_depth (strict). Pixel (row i, column j)
+   backprojects through its centre, p_c = z ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1) (the camera
+   renderer's convention, not the integer keypoints of gc_camera_features_lift), and
+   p_b = R_base_camera p_c + t_base_camera. Per cell over the used pixels, unit weights: n, mean = sum p / n,
+   C = sum (p - mean)(p - mean)^T / n (two passes), zbar the mean of z, and the integer sums of R, G, B.
+   The plane fit and the row are gc_extract_lidar_surfels' from `cov = C + eig_min I` on (the eigenvector of
+   the smallest eigenvalue as the normal, n_z >= 0 in the base frame, the in-plane basis, the Wishart
+   regularisation, kappa, the information form with eps_lift), with w_sum = n and, in the place of
+   sensor_noise_var_per_axis, sigma_z(zbar)^2: sigma_z = sigma0 + slope zbar (depth_model 0) or
+   sigma0 + slope zbar^2 (1). A cell is valid iff n >= max(3, ceil(min_fill cell_px^2)),
+   lambda_min(C) <= (plane_gate sigma_z(zbar))^2 (lambda_min(C) as the fit's smallest eigenvalue less eig_min)
+   and |n . (mean - t_base_camera)| / |mean - t_base_camera| >= min_cos_incidence.
+   Row: weights = weight_scale n / cell_px^2, timestamps = timestamp_sec, sources = 0, colors = (sum R,
+   sum G, sum B) / (255 n) or, with d_rgb8 NULL, the LiDAR rows' grey 0.25 + 0.25 (n_z + 1); lobes 1.. of
+   etas zero, valid_mask 1. Selection: free = n_feat - n_camera_valid_in, V the valid cells in ascending
+   cell id; V <= free keeps all, otherwise the cell of rank r is kept iff floor((r + 1) free / V) >
+   floor(r free / V), which keeps exactly `free` cells spread evenly over the image. The kept cell of
+   kept-rank k goes to row n_camera_valid_in + k with source_indices = row.
+   Outputs (device, caller-allocated and caller-filled, as gc_extract_lidar_surfels lays them out): only the
+   kept rows of the nine arrays are written. d_slot_cells (int32, n_feat) receives the cell id of every row
+   written and -1 for every other row of [0, n_feat). h_n_valid (host) = the kept count; the call waits for
+   it. With free = 0 or no valid cell only d_slot_cells is written. All sums run in a fixed order: the
+   batch is bitwise reproducible. GC_ERR_ARG before any launch for H or W outside [1, 16384], H W >
+   GC_IMAGE_MAX_PIXELS, cell_px outside [4, 32], more than GC_SURFEL_MAX_CELLS cells, n_camera_valid_in
+   outside [0, n_feat], min_fill outside (0, 1], min_depth < 0 or min_depth >= max_depth, depth_model not 0
+   or 1, sigma0 <= 0, slope < 0, plane_gate <= 0, min_cos_incidence outside [0, 1), n_lobes outside [1, 8],
+   fx or fy = 0, a non-finite parameter, intrinsic, R or t, or NULL pointers. */
+int32_t gc_extract_depth_surfels(gc_ctx* ctx, const float* d_depth, const uint8_t* d_rgb8, int32_t H, int32_t W,
+                                 const double* h_intrinsics, const double* h_R_base_camera, const double* h_t_base_camera,
+                                 double timestamp_sec, int32_t n_camera_valid_in, const gc_surfel_cfg* cfg, int32_t cell_px,
+                                 double min_fill, double min_depth, double max_depth, int32_t depth_model, double sigma0,
+                                 double slope, double plane_gate, double min_cos_incidence, double weight_scale,
+                                 double* d_Lambdas, double* d_thetas, double* d_etas, double* d_weights_out,
+                                 int32_t* d_sources, int32_t* d_source_indices, uint8_t* d_valid_mask,
+                                 double* d_timestamps_out, double* d_colors, int32_t* d_slot_cells, int32_t* h_n_valid);
+
 /* LidarCameraDepthFusionConfig in field order (frontend/sensors/lidar_camera_depth_fusion.py:29-63) */
 typedef struct {
   double depth_fusion_weight_camera;
